@@ -9,7 +9,11 @@ step s are copied device-to-device from a 64-step ring of synthetic action
 tapes resident in HBM.  Inputs are resident before the timed
 region; nothing is skipped inside it.
 
-Also reported (one JSON line on rank 0):
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --dump-outputs DIR also writes what the last timed step left in the
+trainInterface outputs (a fixed sample of worlds) as DIR/<name>.npy.
+
+With --full, also reported (one JSON line on rank 0):
   roofline     -- dominant kernel's algorithmic HBM bytes / its average
                   duration (HIP events on the engine's stream, timed
                   region), against the 8 TB/s HBM3E peak; `traffic` = PMC
@@ -19,7 +23,7 @@ Also reported (one JSON line on rank 0):
                   ThreadPoolExecutor path, oracle/) timed on this host on a
                   bounded sample of the same workload, rank 0, N=1 only.
 
-Launch: python bench.py [--gpus 1 --steps 1000 --warmup 100]
+Launch: python bench.py [--gpus 1 --steps 1000 --warmup 100] [--full] [--dump-outputs DIR]
         N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 """
 import argparse
@@ -37,6 +41,8 @@ sys.path.insert(0, PKG)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md §HBM)
 RING = 64
 TAPE_SEED = 1234
+DUMP_BUDGET = 48 << 20  # --dump-outputs: bytes written, all files together
+DUMP_SEED = 2024  # --dump-outputs: draws the sampled worlds
 
 # Algorithmic HBM bytes per agent-step for each kernel: the
 # unique bytes the kernel must read or write, no re-reads counted.
@@ -76,7 +82,15 @@ def parse():
     ap.add_argument("--world-groups", type=int, default=1,
                     help="world ranges stepped on concurrent streams in the timed pass (engine option); "
                          "the profile pass always runs one group so kernel times are exclusive")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed pass, also run the profile passes (roofline, kernels_ms, step_hbm, "
+                         "workload) and the CPU baseline; a plain run reports the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the trainInterface outputs of the last timed step as "
+                         "DIR/<name>.npy (float32, integers as float64; whole worlds drawn by a fixed seed "
+                         f"when the batch exceeds {DUMP_BUDGET >> 20} MB)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="--full: auto = time the CPU oracle on this host")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline timed budget")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPUs this process may use")
     ap.add_argument("--exchange", choices=["auto", "none", "gather", "wire", "local"], default="auto",
@@ -116,7 +130,7 @@ def parse():
                     help="--exchange wire: the learner unpacks on the step stream (back to back with its own "
                          "step) instead of its own unpack stream")
     ap.add_argument("--no-profile-pass", action="store_true",
-                    help="skip the second (kernel-timing + workload-counter) pass")
+                    help="--full: skip the second (kernel-timing + workload-counter) pass")
     ap.add_argument("--bots", choices=["none", "team1", "all"], default="none",
                     help="A* scripted bots (AgentPolicy -1, planAStarAISystem) for team 1 / everyone "
                          "(config C5's nav-mesh pathing); the headline C3 line uses none")
@@ -278,7 +292,43 @@ def stream_buffers(sim, ring, dev):
     nbytes = sum(t.numel() * t.element_size() for t in ins.values()) + \
         sum(t.numel() * t.element_size() for t in outs.values())
     assert disc[0].numel() == A * 4
-    return ptrs, nbytes, keep
+    return ptrs, nbytes, keep, dict(zip(outs, obufs))
+
+
+def dump_outputs(path, tensors, W, prefix=""):
+    """--dump-outputs: the device tensors a caller of the timed path holds
+    after its last step, as path/<name>.npy.  Floats stay float32 (bit for
+    bit), integers become float64 (exact).  Tensors are laid out world by
+    world; when everything together would exceed DUMP_BUDGET, the same
+    worlds of every tensor are kept, drawn once from DUMP_SEED, so two runs
+    with the same arguments write the same rows."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+
+    def width(t):  # bytes per element as written
+        return 4 if t.dtype.is_floating_point else 8
+
+    by_world = {n: t for n, t in tensors.items() if t.dim() > 0 and t.shape[0] % W == 0}
+    fixed = sum(t.numel() * width(t) for n, t in tensors.items() if n not in by_world)
+    per_world = sum(t.numel() // W * width(t) for t in by_world.values())
+    keep = W if per_world == 0 else min(W, max(1, (DUMP_BUDGET - fixed) // per_world))
+    worlds = None
+    if keep < W:
+        worlds = np.sort(np.random.default_rng(DUMP_SEED).choice(W, keep, replace=False))
+    for n, t in tensors.items():
+        if t.dtype == torch.uint32:
+            t = t.view(torch.int32)  # same bits; indexing wants a signed type
+            as_np = lambda a: a.view(np.uint32)
+        else:
+            as_np = lambda a: a
+        if worlds is not None and n in by_world:
+            k = t.shape[0] // W  # rows per world
+            rows = (worlds[:, None] * k + np.arange(k)[None, :]).ravel()
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = as_np(t.contiguous().cpu().numpy())
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        np.save(os.path.join(path, prefix + n + ".npy"), a)
 
 
 def main():
@@ -387,11 +437,11 @@ def main():
         learner = make_exchange(exchange, sim, group=xgroup)
 
     policy = make_policy(sim, args.policy_hidden, dev) if args.actions == "policy" and sim is not None else None
-    stream_ptrs = None
+    stream_ptrs = stream_outs = None
     if args.path == "stream" and sim is not None:
         if args.actions != "tape":
             raise SystemExit("--path stream runs the tape actions only")
-        stream_ptrs, stream_bytes, _keep = stream_buffers(sim, ring, dev)
+        stream_ptrs, stream_bytes, _keep, stream_outs = stream_buffers(sim, ring, dev)
 
     def one_step(s, exchange_on=True):
         if learner_only:
@@ -443,7 +493,14 @@ def main():
     value = total_agent_steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
 
-    # ---- profile passes (not part of `value`): the same episode window
+    if args.dump_outputs and sim is not None:
+        # what the last timed step handed its caller: the caller's buffers on
+        # the stream path, else the engine's zero-copy trainInterface outputs
+        outs = stream_outs if stream_outs is not None else \
+            {n: t.to_torch() for n, t in sim.train_interface()["outputs"].items()}
+        dump_outputs(args.dump_outputs, outs, W, prefix="" if world_size == 1 else f"rank{rank}.")
+
+    # ---- profile passes (--full; not part of `value`): the same episode window
     # again (Manager::init, W warmup steps, K steps) with ONE world group, so
     # every kernel runs alone and its HIP-event duration is exclusive; then
     # once more with the kernels' workload counters on (their atomics slow
@@ -451,7 +508,7 @@ def main():
     # The exchange is not part of these passes (their windows restart the
     # episode; the learner's shadows are left as the timed pass left them).
     prof_pass = None
-    if not args.no_profile_pass and not learner_only:
+    if args.full and not args.no_profile_pass and not learner_only:
         if learner is not None:
             learner.drain()
         sim.set_world_groups(1)
@@ -603,7 +660,7 @@ def main():
         if rank == 0:
             result.update(obj[0])
             result["profile_rank"] = 1
-    if rank == 0 and world_size == 1 and args.cpu_baseline == "auto":
+    if args.full and rank == 0 and world_size == 1 and args.cpu_baseline == "auto":
         result["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(result), file=line_out, flush=True)

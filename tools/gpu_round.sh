@@ -13,7 +13,7 @@ cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 TAG=${TAG:?set TAG}
 WHAT=${1:-all}
-B="timeout -k 10 300 python3 bench.py"
+B="timeout -k 10 300 python3 bench.py --full"  # the lines keep kernels_ms and the CPU baseline
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
     $B --steps 20 --warmup 5 --cpu-baseline off > gpurun_out/${TAG}_bench_short.json && \
     $B > gpurun_out/${TAG}_bench.json && \

@@ -1,7 +1,7 @@
 """Condense a tools/profile_round.sh run into tracked files under profiles/.
 
   profiles/<tag>_kernel_stats.csv  -- rocprofv3 --kernel-trace --stats summary of
-                                      the default bench command (every launch)
+                                      the bench command with --full (every launch)
   profiles/<tag>_kernels.json      -- per kernel, over the bench command's
                                       exclusive-timing window (its profile pass:
                                       whole-batch launches, warmup excluded):
@@ -70,7 +70,7 @@ def main(tag, src):
         if os.path.exists(p):
             pmc.update(counters(p))
     out = {"tag": tag, "workload": bench["config"]["workload"], "bench_command_window":
-           f"profile pass of `bench.py --cpu-baseline off`: whole-batch launches {warm}..{warm + steps - 1}",
+           f"profile pass of `bench.py --full --cpu-baseline off`: whole-batch launches {warm}..{warm + steps - 1}",
            "kernels": {}}
     for k, lst in sorted(disp.items()):
         lst.sort()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles the bench workload on the GPU box (run under gpurun):
-#   1. rocprofv3 --kernel-trace --stats of the default bench command itself
+#   1. rocprofv3 --kernel-trace --stats of the bench command with --full
 #      (its profile pass launches every kernel over the whole batch; the
 #      summary tool averages those launches for comparison with the bench
 #      line's launch_ms)
@@ -17,7 +17,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- \
-    python3 bench.py --cpu-baseline off $BENCH_ARGS > $OUT/trace_bench.json && \
+    python3 bench.py --full --cpu-baseline off $BENCH_ARGS > $OUT/trace_bench.json && \
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o run -- \
     python3 bench.py $PMC_ARGS > $OUT/fetch_bench.json && \
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o run -- \
