@@ -469,6 +469,11 @@ int mpenv_world_groups(mpenv_manager *mgr, int32_t *groups);
  * k_vis -> k_obs (fork after k_sim, join at the end of the step; results
  * identical).  Default off; env MPENV_LIDAR_BRANCH=1 at creation. */
 int mpenv_set_lidar_branch(mpenv_manager *mgr, int32_t on);
+/* Extension: how many wave tasks of the lidar kernel a block's 16 waves
+ * share, per wave.  0 = automatic (from the batch size, the default),
+ * 1..12 forces the value; anything else is MPENV_ERR_INVALID.  Results are
+ * identical for every value; the step graph is re-captured on a change. */
+int mpenv_set_lidar_iters(mpenv_manager *mgr, int32_t n);
 
 /* Manager::triggerReset (mgr.cpp:2484-2500) */
 int mpenv_trigger_reset(mpenv_manager *mgr, int32_t world_idx);

@@ -320,7 +320,11 @@ struct WireObs {
     int32_t keyframe;        // a keyframe carries the last-known rows: nothing is cleared
 };
 int launchObservationsWire(const DevState &view, const SceneDev &sc, const WireObs &wo, void *stream);
-int launchLidar(const DevState &s, const SceneDev &sc, void *stream);
+// k_lidar: a block's 16 waves share `iters` x 16 wave tasks, 1 <= iters <=
+// lidarItersMax(); lidarItersFor is the automatic choice for A agents.
+int lidarItersMax();
+int lidarItersFor(int64_t A);
+int launchLidar(const DevState &s, const SceneDev &sc, int iters, void *stream);
 // synchronous on `stream`, at scene upload; dev_scratch holds kMaxZones ints
 int computeZoneGoalTris(const SceneDev &sc, int32_t *dev_scratch, int32_t *host_out, void *stream);
 int launchTraceRays(const SceneDev &sc, const float *o, const float *d, int n, int mode, float *t, int32_t *hit,

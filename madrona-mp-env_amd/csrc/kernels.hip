@@ -3926,17 +3926,24 @@ k_obs(DevState S, SceneDev sc, WireObs wo)
 // Against 64 consecutive rays of the flat [agent][80] order (which straddle
 // two agents in 4 of 5 waves) this cuts the wave-lockstep node iterations by
 // ~12% and triangle tests by ~19% (tools/trav_stats.cpp on recorded rays);
-// every lane's arithmetic is unchanged.  A block's 4 waves take `iters`
-// consecutive task quads: up to kLidarIters (amortises the BVH staging) on
-// big batches, fewer on small ones so the grid still spreads over the CUs
-// (at 64 worlds 1v1 a fixed 8 put the whole lidar on 5 CUs).
-constexpr int kLidarIters = 6; // round 5, one world group: 4: 0.665, 5: 0.642, 6: 0.643 ms steady, step 1.185 / 1.168 / 1.163 ms (profiles/r05m_lab_lidar_iters.jsonl; round 2: 1: 0.98, 2: 0.91, 4: 0.89, 8: 0.92 ms)
+// every lane's arithmetic is unchanged.  A block owns `iters` x 16
+// consecutive tasks and its 16 waves draw them one at a time from a counter
+// in LDS, so a wave that drew short tasks takes more of them and the block's
+// LDS image is not held for the wave with the longest fixed share (DESIGN.md
+// §4, "k_lidar's task scheduling").  `iters` is up to kLidarItersAuto (amortises the BVH staging) on big
+// batches, fewer on small ones so the grid still spreads over the CUs (at 64
+// worlds 1v1 a fixed 8 put the whole lidar on 5 CUs): lidarItersFor.
+constexpr int kLidarIters = 12;    // compiled maximum of tasks per wave (mpenv_set_lidar_iters)
+constexpr int kLidarItersAuto = 6; // what launchLidar's caller gets on big batches: round 5, one world group: 4: 0.665, 5: 0.642, 6: 0.643 ms steady (profiles/r05m_lab_lidar_iters.jsonl; round 2: 1: 0.98, 2: 0.91, 4: 0.89, 8: 0.92 ms)
 // 1024-thread blocks: the 8 octant node images + the three rotated vertex
 // copies (31 + 36 KB on simple_map) are staged once per 16 waves, so 2
-// blocks per CU (8 waves per SIMD) fit the 160 KB of LDS.
+// blocks per CU (8 waves per SIMD) fit the 160 KB of LDS: 67 KB of image
+// plus 9,168 B of static LDS (the agent stage, sized for kLidarIters = 12
+// tasks per wave: 8,832 B; 5,376 B when the maximum was 6) is ~76 KB per
+// block, 152 KB for two, 8 KB of headroom.
 constexpr int kLidarBlock = 1024;
 constexpr int kLidarWaves = kLidarBlock / 64;
-constexpr int kLidarStageMax = 112, kLidarStageCols = 12; // k_lidar's per-block agent stage
+constexpr int kLidarStageMax = 184, kLidarStageCols = 12; // k_lidar's per-block agent stage
 static_assert(4 * ((kLidarIters * kLidarWaves) / 5 + 2) + 2 * (2 * kMaxTeamSize - 1) <= kLidarStageMax,
               "k_lidar agent stage");
 
@@ -3978,9 +3985,10 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
     const uint32_t ntasks = (uint32_t)lidarTasks(S.A);
     // The agents this block's tasks read -- the rays' origins and frames and
     // every capsule of their worlds -- staged in LDS with the BVH: whole
-    // worlds around the block's task range (<= 14 units of 4 agents plus a
-    // partial world at each end: <= 78 agents, N <= 12), so no task waits
-    // on HBM for them.
+    // worlds around the block's task range (at kLidarIters = 12: <= 40 units
+    // of 4 agents plus a partial world at each end: <= 182 agents, N <= 12;
+    // the automatic 6: <= 21 units, <= 106 agents), so no task waits on HBM
+    // for them.
     __shared__ float agentStage[kLidarStageCols][kLidarStageMax];
     const uint32_t t0 = xcdBlockId() * (uint32_t)iters * kLidarWaves;
     const uint32_t t1 = min(ntasks, t0 + (uint32_t)iters * kLidarWaves);
@@ -4005,13 +4013,40 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
             agentStage[11][k] = viewHeightD(S.curPose[g]);
         }
     }
-    // gpuStreamStep's caller buffers (engine.h OutTab), read once with the staging
-    const OutTab *ot = (S.outTab && S.outTab->on) ? S.outTab : nullptr;
+    // gpuStreamStep's caller buffers (engine.h OutTab), read once per block
+    // into wave-uniform values (off: all null), held in scalar registers
+    // across the traversals
+    float4 *oFwd = nullptr, *oRear = nullptr, *oMap0 = nullptr, *oMap1 = nullptr;
+    if (S.outTab && S.outTab->on) {
+        auto uniform = [](const float *p) {
+            const uint64_t v = reinterpret_cast<uint64_t>(p);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+            return reinterpret_cast<float4 *>(((uint64_t)hi << 32) | lo);
+        };
+        oFwd = uniform(S.outTab->fwdLidar);
+        oRear = uniform(S.outTab->rearLidar);
+        oMap0 = uniform(S.outTab->agentMap0);
+        oMap1 = uniform(S.outTab->agentMap1);
+    }
+    // The block's tasks are dealt from this counter: wave v starts with task
+    // v of the block; a wave that is free draws the next one (one LDS atomic
+    // by lane 0, broadcast), and leaves when the range is used up.  No wave
+    // ever waits for another.  With one task per wave nothing is drawn.
+    __shared__ uint32_t nextTask;
+    if (threadIdx.x == 0) nextTask = kLidarWaves;
     const LBVH bvh = stageBVHOct(smem, sc); // ends with __syncthreads
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int it = 0; it < iters; it++) {
-        const uint32_t task = (xcdBlockId() * iters + it) * kLidarWaves + wave; // wave-uniform
-        if (task >= ntasks) break;
+    auto draw = [&]() {
+        if (iters == 1) return (uint32_t)kLidarWaves;
+        // the lane id read here (volatile, as in the loop body): hoisted out
+        // of the loop it lived across the traversal and was spilled
+        uint32_t ln, drawn = 0u;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        if (ln == 0u) drawn = atomicAdd(&nextTask, 1u);
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn);
+    };
+    for (uint32_t k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); t0 + k < t1; k = draw()) {
+        const uint32_t task = t0 + k; // wave-uniform
         const uint32_t unit = task / 5u, sub = task - unit * 5u;
         const bool fwd = sub < 4u;
         // The ray of lane `ln`: a tail unit's lanes past A trace a copy of
@@ -4019,7 +4054,7 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
         auto rayIndex = [&](uint32_t ln, uint32_t &g, bool &valid, uint32_t &kk) {
             const uint32_t g_raw = unit * 4u + (fwd ? sub : (ln >> 4));
             valid = g_raw < A;
-            g = valid ? g_raw : A - 1u;
+            g = min(g_raw, A - 1u); // (a min with a scalar: a select kept A - 1 in a VGPR across the loop)
             kk = fwd ? ln : (ln & 15u); // ray slot within the forward / rear fan
         };
         auto makeRay = [&](uint32_t ln, uint32_t &g, bool &valid, uint32_t &kk, Vec3 &ray_o, Vec3 &dir) {
@@ -4206,7 +4241,9 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
                            : reinterpret_cast<float4 *>(S.ftRearLidar) + slot * kRearRays + kk;
         // fullTeamObservationsSystem copies the lidar before this system
         // overwrites it (sim.cpp:5283-5310): the previous value moves into
-        // the team interface's slot.
+        // the team interface's slot.  (Moving this copy into a block
+        // prologue, so that the loop loads nothing, measured slower:
+        // DESIGN.md §4, "k_lidar's task scheduling".)
         *tdst = *dst;
         *dst = out;
         // gpuStreamStep: the caller's lidar buffer too (the engine's copy is
@@ -4214,15 +4251,14 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
         // agent's two agent maps zero-filled by its forward wave (4 KB each:
         // 4 store instructions of 64 x 16 B per map, no loads; the stores
         // drain while the wave's next traversal runs)
-        if (ot) {
+        if (oFwd) {
             const int64_t gb = S.outBase + (int64_t)g;
-            float4 *cdst = fwd ? reinterpret_cast<float4 *>(ot->fwdLidar) + gb * kFwdRays + kk
-                               : reinterpret_cast<float4 *>(ot->rearLidar) + gb * kRearRays + kk;
+            float4 *cdst = fwd ? oFwd + gb * kFwdRays + kk : oRear + gb * kRearRays + kk;
             *cdst = out;
             if (fwd) {
                 const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 *m0 = reinterpret_cast<float4 *>(ot->agentMap0) + gb * 256 + kk;
-                float4 *m1 = reinterpret_cast<float4 *>(ot->agentMap1) + gb * 256 + kk;
+                float4 *m0 = oMap0 + gb * 256 + kk;
+                float4 *m1 = oMap1 + gb * 256 + kk;
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     m0[64 * q] = z;
@@ -4519,11 +4555,22 @@ int computeZoneGoalTris(const SceneDev &sc, int32_t *dev_scratch, int32_t *host_
     return rc;
 }
 
-int launchLidar(const DevState &s, const SceneDev &sc, void *stream)
+int lidarItersMax() { return kLidarIters; }
+
+// k_lidar's automatic tasks per wave for a batch of A agents: ~1024 blocks
+// before the value grows past 1, so the grid still spreads over the CUs, and
+// kLidarItersAuto at most (C3 with the waves drawing their tasks: 6: 0.579 ms,
+// 10, the value with the fewest dispatch rounds on 256 CUs: 0.596 ms, DESIGN.md
+// §4; larger values are for mpenv_set_lidar_iters).
+int lidarItersFor(int64_t A)
 {
-    // ~1024 blocks before the iterations grow past 1
+    return (int)std::max<int64_t>(1, std::min<int64_t>(kLidarItersAuto, lidarTasks(A) / (kLidarWaves * 1024)));
+}
+
+int launchLidar(const DevState &s, const SceneDev &sc, int iters, void *stream)
+{
+    if (iters < 1 || iters > kLidarIters) return -1; // the agent stage is sized for kLidarIters
     const int64_t tasks = lidarTasks(s.A);
-    const int iters = (int)std::max<int64_t>(1, std::min<int64_t>(kLidarIters, tasks / (kLidarWaves * 1024)));
     const int64_t per_block = (int64_t)kLidarWaves * iters;
     const int blocks = (int)((tasks + per_block - 1) / per_block);
     hipLaunchKernelGGL(k_lidar, dim3(blocks), dim3(kLidarBlock), bvhLdsBytesOct(sc), (hipStream_t)stream, s, sc,

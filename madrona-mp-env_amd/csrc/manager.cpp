@@ -127,6 +127,10 @@ struct mpenv_manager {
     bool lidarBranch = false;
     hipStream_t bStream = nullptr;
     hipEvent_t bForkEv = nullptr, bJoinEv = nullptr;
+    // k_lidar's tasks per wave: 0 = lidarItersFor(agents of the range), else
+    // forced (mpenv_set_lidar_iters)
+    int lidarIters = 0;
+    int lidarItersOf(const DevState &R) const { return lidarIters ? lidarIters : lidarItersFor(R.A); }
     // gpuStreamStep: the agent maps' zero fills (no dependence on the step)
     // on a side stream of their own, overlapping the step's kernels; joined
     // back into the caller's stream before the call returns.
@@ -252,7 +256,7 @@ struct mpenv_manager {
         if (lidarBranch && groups == 1 && !timing) {
             HIP_CHECK(hipEventRecord(bForkEv, st));
             HIP_CHECK(hipStreamWaitEvent(bStream, bForkEv, 0));
-            if (launchLidar(R, rsc, bStream)) throw std::runtime_error("k_lidar launch failed");
+            if (launchLidar(R, rsc, lidarItersOf(R), bStream)) throw std::runtime_error("k_lidar launch failed");
             HIP_CHECK(hipEventRecord(bJoinEv, bStream));
             if (launchVisibility(R, rsc, st)) throw std::runtime_error("k_vis launch failed");
             if (launchObservations(R, rsc, st)) throw std::runtime_error("k_obs launch failed");
@@ -263,7 +267,7 @@ struct mpenv_manager {
         record(st);
         if (launchObservations(R, rsc, st)) throw std::runtime_error("k_obs launch failed");
         record(st);
-        if (launchLidar(R, rsc, st)) throw std::runtime_error("k_lidar launch failed");
+        if (launchLidar(R, rsc, lidarItersOf(R), st)) throw std::runtime_error("k_lidar launch failed");
         record(st);
     }
 
@@ -320,6 +324,7 @@ struct mpenv_manager {
         };
         put(&groups, sizeof(groups));
         put(&lidarBranch, sizeof(lidarBranch));
+        put(&lidarIters, sizeof(lidarIters));
         put(&S, sizeof(S));
         put(&sc, sizeof(sc));
         for (const DevState &G : gS) put(&G, sizeof(G));
@@ -428,7 +433,7 @@ struct mpenv_manager {
         if (launchResetOnly(S, sc, st)) throw std::runtime_error("k_reset launch failed");
         if (launchVisibility(S, sc, st)) throw std::runtime_error("k_vis launch failed");
         if (launchObservations(S, sc, st)) throw std::runtime_error("k_obs launch failed");
-        if (launchLidar(S, sc, st)) throw std::runtime_error("k_lidar launch failed");
+        if (launchLidar(S, sc, lidarItersOf(S), st)) throw std::runtime_error("k_lidar launch failed");
     }
 
     bool exportDesc(int32_t id, TensorDesc &d);
@@ -1493,6 +1498,16 @@ int mpenv_set_lidar_branch(mpenv_manager *m, int32_t on)
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
     }
+    return MPENV_OK;
+}
+
+int mpenv_set_lidar_iters(mpenv_manager *m, int32_t n)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null argument");
+    if (n < 0 || n > lidarItersMax())
+        return fail(MPENV_ERR_INVALID, "lidar iters must be 0 (automatic) or in [1, " + std::to_string(lidarItersMax()) + "]");
+    // a kernel argument: the step graph is keyed on it (argKey) and re-captured
+    m->lidarIters = n;
     return MPENV_OK;
 }
 

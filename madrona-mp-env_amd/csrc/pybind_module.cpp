@@ -276,6 +276,7 @@ PYBIND11_MODULE(madrona_mp_env, m)
         }, py::arg("out"), py::arg("stream"))
         .def("set_world_groups", [](PySimManager &s, int32_t g) { check(mpenv_set_world_groups(s.h->mgr, g)); })
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
+        .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
         .def("graph_status", [](PySimManager &s) {
             int32_t on = 0;
             char why[512] = {};

@@ -157,6 +157,10 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
                         None, 0)
     h = C.c_void_p()
     assert lib.mpenv_create(C.byref(cfg), C.byref(h)) == 0, lib.mpenv_last_error()
+    if os.environ.get("LAB_LIDAR_ITERS"):
+        # k_lidar's tasks per wave forced (mpenv_set_lidar_iters; 0 or unset: automatic)
+        lib.mpenv_set_lidar_iters.argtypes = [C.c_void_p, C.c_int32]
+        assert lib.mpenv_set_lidar_iters(h, int(os.environ["LAB_LIDAR_ITERS"])) == 0, lib.mpenv_last_error()
     # simCtrl [0, 1, 1] as bench.py (random start step and team sides)
     lib.mpenv_export_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]

@@ -9,6 +9,11 @@
 //       temporal-hint model: PREV holds the same ray slots one step earlier
 //       (tools/dump_lidar_rays.py at step s - 1); each ray first tests the
 //       triangle its slot hit then and starts with t_max = that hit's t
+//   TRAV_SCHED=1 trav_stats SCENE_DIR RAYS.f32
+//       k_lidar's task scheduling on the shipped lidar tree: how long a block
+//       of 16 waves lives against its mean wave work, tasks dealt statically
+//       or drawn by the wave that is free, for 6..12 tasks per wave
+//       (schedMain; TRAV_SCHED_CONST=c adds c to every task's cost)
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -810,7 +815,8 @@ struct KM {
 static bool g_deferTris = false; // TRAV_DEFER: every slot's box test at the node's entry t_max, then the triangles
 
 static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &vt, const std::vector<float> &rays,
-                        bool fwd_waves, KM &km, const std::vector<float> *ref_t = nullptr, std::vector<float> *out_t = nullptr)
+                        bool fwd_waves, KM &km, const std::vector<float> *ref_t = nullptr, std::vector<float> *out_t = nullptr,
+                        std::vector<double> *wave_cost = nullptr) // [n / 64] weighted cost of each wave of this kind
 {
     const size_t n = rays.size() / 6;
     // octant slot orders
@@ -910,6 +916,7 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
             }
         }
         km.nodeIters += mp;
+        const double triBefore = km.triIters;
         for (size_t it = 0; it < mp; it++) {
             for (int k = 0; k < 4; k++) {
                 int m = 0;
@@ -922,7 +929,64 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
                 if (it < L.size()) mm = std::max(mm, L[it][0] + L[it][1] + L[it][2] + L[it][3]);
             km.triItersMerged += mm;
         }
+        if (wave_cost) (*wave_cost)[w0 / 64] = 110.0 * mp + 45.0 * (km.triIters - triBefore);
     }
+}
+
+// ---- TRAV_SCHED: k_lidar's task loop.  A block of 16 waves owns iters x 16
+// consecutive wave tasks (the ray file's order: 4 forward waves, then 1 rear)
+// and keeps its LDS image until its last wave ends.  Static deal: wave w runs
+// tasks w, w + 16, ...  Dynamic: the tasks are drawn in order, each by the
+// wave that is free first.  Printed: sum of block lifetimes / sum of mean wave
+// work (1.0 = no wave-slot time lost waiting for the slowest wave), with
+// kernelModel's cost per task on the shipped lidar tree.
+static int schedMain(const char *scene, const std::vector<float> &rays)
+{
+    int32_t nn = 0, nv = 0, ms = 0;
+    if (mpenv_scene_lidar_bvh(scene, nullptr, &nn, nullptr, &nv, &ms)) return 1;
+    std::vector<Node> nd(nn);
+    std::vector<float> vt((size_t)nv * 3);
+    if (mpenv_scene_lidar_bvh(scene, nd.data(), &nn, vt.data(), &nv, &ms)) return 1;
+    const size_t ntasks = rays.size() / 6 / 64;
+    std::vector<double> cost(ntasks, 0.0);
+    KM f, r;
+    kernelModel(nd, vt, rays, true, f, nullptr, nullptr, &cost);
+    kernelModel(nd, vt, rays, false, r, nullptr, nullptr, &cost);
+    const double extra = getenv("TRAV_SCHED_CONST") ? atof(getenv("TRAV_SCHED_CONST")) : 0.0;
+    double sum[2] = { 0, 0 }, sq[2] = { 0, 0 }, cnt[2] = { 0, 0 };
+    for (size_t t = 0; t < ntasks; t++) {
+        const int rear = (t % 5) == 4;
+        sum[rear] += cost[t];
+        sq[rear] += cost[t] * cost[t];
+        cnt[rear]++;
+        cost[t] += extra;
+    }
+    for (int k = 0; k < 2; k++) {
+        const double m = sum[k] / std::max(cnt[k], 1.0);
+        printf("%s task: mean cost %.0f, s.d. %.0f (%.0f tasks)\n", k ? "rear" : "forward", m,
+               std::sqrt(std::max(0.0, sq[k] / std::max(cnt[k], 1.0) - m * m)), cnt[k]);
+    }
+    printf("block lifetime / mean wave work, 16 waves per block, +%.0f per task\n", extra);
+    printf("| tasks per wave | static deal | waves draw the next task when free |\n|---|---|---|\n");
+    const int W = 16;
+    for (int iters = 6; iters <= 12; iters++) {
+        const size_t per = (size_t)W * iters;
+        double lifeS = 0, lifeD = 0, mean = 0;
+        for (size_t b0 = 0; b0 < ntasks; b0 += per) {
+            const size_t b1 = std::min(ntasks, b0 + per);
+            double st[W] = {}, dy[W] = {}, work = 0;
+            for (size_t t = b0; t < b1; t++) {
+                st[(t - b0) % W] += cost[t];
+                *std::min_element(dy, dy + W) += cost[t];
+                work += cost[t];
+            }
+            lifeS += *std::max_element(st, st + W);
+            lifeD += *std::max_element(dy, dy + W);
+            mean += work / W;
+        }
+        printf("| %d | %.3f | %.3f |\n", iters, lifeS / mean, lifeD / mean);
+    }
+    return 0;
 }
 
 static int treesMain(const char *scene, const std::vector<float> &rays)
@@ -1260,6 +1324,7 @@ int main(int argc, char **argv)
     size_t n = rays.size() / 6;
     g_deferTris = getenv("TRAV_DEFER") != nullptr;
     if (getenv("TRAV_TREES")) return treesMain(argv[1], rays);
+    if (getenv("TRAV_SCHED")) return schedMain(argv[1], rays);
     {
         double un = 0, ut = 0;
         for (size_t w0 = 0; w0 < n; w0 += 64) {
