@@ -386,6 +386,14 @@ int mpenv_export_tensor(mpenv_manager *mgr, int32_t export_id, void **ptr,
                         int32_t *dtype, int32_t *ndim, int64_t *dims,
                         int32_t *gpu_id);
 
+/* dtype and dims mpenv_export_tensor reports for an export of a manager with
+ * num_worlds worlds and team_size agents per team; needs no manager and no
+ * GPU.  dims must hold 8 entries.  The log exports' shapes are given whether
+ * or not their log mode is on (mpenv_export_tensor fails for a log buffer
+ * that was not allocated). */
+int mpenv_export_layout(int32_t export_id, uint32_t num_worlds, uint32_t team_size,
+                        int32_t *dtype, int32_t *ndim, int64_t *dims);
+
 /* TrainInterface (mgr.cpp:2383-2431): number of named inputs / outputs and
  * their (name, export id).  Index order is the gpuStream buffers order. */
 int mpenv_train_interface_size(int32_t *num_inputs, int32_t *num_outputs);

@@ -64,6 +64,117 @@ constexpr int kMaxBVHStack = 16; // register byte-stack capacity
 #define MP_WORLD_F32(X) \
     X(teamRew0) X(teamRew1) X(goalMin0) X(goalMin1) X(goalTeam0) X(goalTeam1)
 
+// The buffer table: every other device buffer of DevState, declared once
+// (dmg, resetKeys and the optional logs apart, see DevState).
+//   X(member, element type, row kind, row shape...)
+//   E(member, element type, row kind, MPENV_EXPORT_* id, row shape...)   exported
+// A row holds the product of its shape in elements.  An exported buffer's
+// tensor dims are its row count followed by that shape, so a trailing 1 is
+// part of it where the reference's dims have one (mgr.cpp:1965-2381).
+// DevState's members, the row:: constants below, and in manager.cpp
+// allocState, sliceState and the export layout / pointers are expansions of
+// these lists: a new buffer is one line here.  A shape may name T (the team
+// size) and trackLen (SceneDev::spawnTrackLen), which the run-time
+// expansions define; exported shapes are compile-time constants.  The lists
+// are in member and allocation order, cut in three where allocState
+// allocates by hand in between.
+enum RowKind {
+    kPerAgent,  // A rows; a world range starts at row w0 * N
+    kPerWorld,  // W rows; at row w0
+    kPerTeam,   // 2 W rows, one per (world, team); at row 2 * w0
+    kUnsliced,  // one row shared by every world range
+};
+
+constexpr int64_t bufRows(RowKind k, int64_t W, int64_t N)
+{
+    return k == kPerAgent ? W * N : k == kPerWorld ? W : k == kPerTeam ? 2 * W : 1;
+}
+
+// first row of the world range that starts at world w0
+constexpr int64_t bufFirstRow(RowKind k, int64_t w0, int64_t N)
+{
+    return k == kUnsliced ? 0 : bufRows(k, w0, N);
+}
+
+template <typename... D>
+constexpr int64_t rowElems(D... d)
+{
+    return (int64_t(1) * ... * int64_t(d));
+}
+
+#define MP_BUFS_A(X, E) \
+    X(visMask, uint8_t, kPerAgent, 1) /* OpponentsVisibility, bit k = sees opponent k */
+
+// visOcc: k_vis occluder hint per (agent, opponent slot, sample point): the
+// triangle that last ended that line-of-sight ray (0xffff: none).  A
+// performance hint only -- any value gives the same answer (geom_dev.h
+// visibleRayD) -- so it is never reset.
+// exploreBits: ExploreTracker tiles for episode exploreEp (the tile
+// exploreTile is current in exploreLo / exploreHi).
+#define MP_BUFS_B(X, E) \
+    X(visOcc, uint16_t, kPerAgent, T, 4) \
+    X(exploreBits, uint64_t, kPerAgent, kExploreTiles) \
+    X(filtLast, int32_t, kPerWorld, 2, 3) /* FiltersMatchState::lastMatches (3 filters used) */ \
+    X(zoneStats, int32_t, kPerWorld, 5, 5)
+
+#define MP_BUFS_C(X, E) \
+    X(spawnTrack, uint32_t, kPerWorld, 3, trackLen) /* SpawnUsageCounter */ \
+    X(crumbs, float4, kPerWorld, kMaxCrumbs, 2) /* {x,y,z,penalty},{team,offset,id,-} */ \
+    /* Exported columns (reference layouts) */ \
+    E(reset, int32_t, kPerWorld, MPENV_EXPORT_RESET, 1) \
+    E(worldCurr, int32_t, kPerWorld, MPENV_EXPORT_WORLD_CURRICULUM, 1) \
+    E(matchResult, int32_t, kPerWorld, MPENV_EXPORT_MATCH_RESULT, 30) \
+    E(exploreAction, int32_t, kPerAgent, MPENV_EXPORT_EXPLORE_ACTION, 4) \
+    E(discreteAction, int32_t, kPerAgent, MPENV_EXPORT_PVP_DISCRETE_ACTION, 4) \
+    E(aimAction, float, kPerAgent, MPENV_EXPORT_PVP_AIM_ACTION, 1, 2) \
+    E(discreteAim, int32_t, kPerAgent, MPENV_EXPORT_PVP_DISCRETE_AIM_ACTION, 2) \
+    E(policy, int32_t, kPerAgent, MPENV_EXPORT_AGENT_POLICY, 1) \
+    X(botAction, int32_t, kPerAgent, 7) \
+    E(reward, float, kPerAgent, MPENV_EXPORT_REWARD, 1) \
+    E(done, int32_t, kPerAgent, MPENV_EXPORT_DONE, 1) \
+    E(selfObs, float, kPerAgent, MPENV_EXPORT_SELF_OBSERVATION, kSelfObs) \
+    E(filters, float, kPerAgent, MPENV_EXPORT_FILTERS_STATE, 1) \
+    E(tmObs, float, kPerAgent, MPENV_EXPORT_TEAMMATE_OBSERVATIONS, 5, kOtherObs) \
+    E(oppObs, float, kPerAgent, MPENV_EXPORT_OPPONENT_OBSERVATIONS, 6, kOtherObs) \
+    E(lkObs, float, kPerAgent, MPENV_EXPORT_OPPONENT_LAST_KNOWN_OBSERVATIONS, 6, kOtherObs) \
+    E(selfPos, float, kPerAgent, MPENV_EXPORT_SELF_POSITION, 3) \
+    E(tmPos, float, kPerAgent, MPENV_EXPORT_TEAMMATE_POSITIONS, 5, 3) \
+    E(oppPos, float, kPerAgent, MPENV_EXPORT_OPPONENT_POSITIONS, 6, 3) \
+    E(lkPos, float, kPerAgent, MPENV_EXPORT_OPPONENT_LAST_KNOWN_POSITIONS, 6, 3) \
+    E(masks, float, kPerAgent, MPENV_EXPORT_OPPONENT_MASKS, 6, 1) \
+    E(fwdLidar, float, kPerAgent, MPENV_EXPORT_FWD_LIDAR, 2, 32, 4) \
+    E(rearLidar, float, kPerAgent, MPENV_EXPORT_REAR_LIDAR, 2, 8, 4) \
+    /* never written, as in the reference; also MPENV_EXPORT_UNMASKED_AGENT_MAP */ \
+    E(agentMap, float, kPerAgent, MPENV_EXPORT_AGENT_MAP, 16, 16, 4) \
+    E(hp, float, kPerAgent, MPENV_EXPORT_HP, 1) \
+    E(alive, float, kPerAgent, MPENV_EXPORT_ALIVE, 1) \
+    E(magazine, int32_t, kPerAgent, MPENV_EXPORT_MAGAZINE, 2) \
+    E(rewardCoefs, float, kPerAgent, MPENV_EXPORT_REWARD_HYPER_PARAMS, 9) \
+    X(trainCtrl, int32_t, kUnsliced, 3) /* MPENV_EXPORT_SIM_CONTROL, dims { 3 } */ \
+    /* FullTeamInterface columns, one row per (world, team) (types.hpp:1040-1152); */ \
+    /* ftActions and ftPolicy are inputs the step never reads */ \
+    E(ftActions, int32_t, kPerTeam, MPENV_EXPORT_FULL_TEAM_ACTIONS, 6, 4) \
+    E(ftGlobal, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_GLOBAL, MPENV_FT_GLOBAL_DIM) \
+    E(ftPlayers, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_PLAYERS, 6, MPENV_FT_PLAYER_DIM) \
+    E(ftEnemies, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_ENEMIES, 6, MPENV_FT_ENEMY_DIM) \
+    E(ftLastKnown, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_LAST_KNOWN_ENEMIES, 6, MPENV_FT_COMMON_DIM) \
+    E(ftFwdLidar, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_FWD_LIDAR, 6, 2, 32, 4) \
+    E(ftRearLidar, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_REAR_LIDAR, 6, 2, 8, 4) \
+    E(ftReward, float, kPerTeam, MPENV_EXPORT_FULL_TEAM_REWARD, 1) \
+    E(ftDone, int32_t, kPerTeam, MPENV_EXPORT_FULL_TEAM_DONE, 1) \
+    E(ftPolicy, int32_t, kPerTeam, MPENV_EXPORT_FULL_TEAM_POLICY_ASSIGNMENTS, 1)
+
+#define MP_BUFS(X, E) MP_BUFS_A(X, E) MP_BUFS_B(X, E) MP_BUFS_C(X, E)
+#define MP_BUF_SKIP(...)
+
+// Elements per row of each exported buffer (row::lkPos == 18, ...)
+namespace row {
+#define MP_ROW(n, type, kind, id, ...) constexpr int n = (int)rowElems(__VA_ARGS__);
+MP_BUFS(MP_BUF_SKIP, MP_ROW)
+#undef MP_ROW
+} // namespace row
+static_assert(row::fwdLidar == kFwdRays * 4 && row::rearLidar == kRearRays * 4, "lidar rows are float4 per ray");
+
 // Agent flag bits (CombatState booleans, types.hpp:510-528)
 enum : int32_t {
     kFlagSuccessfulKill = 1,
@@ -89,61 +200,10 @@ struct DevState {
 #undef MP_DECL_F
 #undef MP_DECL_I
 
-    float *dmg;            // [6][A] DamageDealt
-    uint8_t *visMask;      // [A] OpponentsVisibility, bit k = sees opponent k
-    // [A][T][4] k_vis occluder hint per (agent, opponent slot, sample
-    // point): the triangle that last ended that line-of-sight ray (0xffff:
-    // none).  A performance hint only -- any value gives the same answer
-    // (geom_dev.h visibleRayD) -- so it is never reset.
-    uint16_t *visOcc;
-    uint64_t *exploreBits; // [A][kExploreTiles] ExploreTracker tiles for episode exploreEp
-                           // (the tile exploreTile is current in exploreLo / exploreHi)
-    int32_t *filtLast;     // [W][2][3] FiltersMatchState::lastMatches (3 filters used)
-    int32_t *zoneStats;    // [W][5][5]
-    uint32_t *spawnTrack;  // [W][3][spawnTrackLen] SpawnUsageCounter
-    float4 *crumbs;        // [W][kMaxCrumbs][2] {x,y,z,penalty},{team,offset,id,-}
-
-    // Exported columns (reference layouts)
-    int32_t *reset;        // [W]
-    int32_t *worldCurr;    // [W]
-    int32_t *matchResult;  // [W][30]
-    int32_t *exploreAction;// [A][4]
-    int32_t *discreteAction; // [A][4]
-    float *aimAction;      // [A][2]
-    int32_t *discreteAim;  // [A][2]
-    int32_t *policy;       // [A]
-    int32_t *botAction;    // [A][7]
-    float *reward;         // [A]
-    int32_t *done;         // [A]
-    float *selfObs;        // [A][43]
-    float *filters;        // [A]
-    float *tmObs;          // [A][5][32]
-    float *oppObs;         // [A][6][32]
-    float *lkObs;          // [A][6][32]
-    float *selfPos;        // [A][3]
-    float *tmPos;          // [A][5][3]
-    float *oppPos;         // [A][6][3]
-    float *lkPos;          // [A][6][3]
-    float *masks;          // [A][6]
-    float *fwdLidar;       // [A][2][32][4]
-    float *rearLidar;      // [A][2][8][4]
-    float *agentMap;       // [A][16][16][4] (never written, as in the reference)
-    float *hp;             // [A]
-    float *alive;          // [A]
-    int32_t *magazine;     // [A][2]
-    float *rewardCoefs;    // [A][9]
-    int32_t *trainCtrl;    // [3]
-    // FullTeamInterface columns, one row per (world, team) (types.hpp:1040-1152)
-    int32_t *ftActions;    // [W*2][6][4] (input, never read by the step)
-    float *ftGlobal;       // [W*2][16]
-    float *ftPlayers;      // [W*2][6][28]
-    float *ftEnemies;      // [W*2][6][33]
-    float *ftLastKnown;    // [W*2][6][24]
-    float *ftFwdLidar;     // [W*2][6][64][4]
-    float *ftRearLidar;    // [W*2][6][16][4]
-    float *ftReward;       // [W*2]
-    int32_t *ftDone;       // [W*2]
-    int32_t *ftPolicy;     // [W*2] (input, never read by the step)
+    float *dmg;            // [6][A] DamageDealt, row stride dmgStride
+#define MP_DECL(n, type, ...) type *n;
+    MP_BUFS(MP_DECL, MP_DECL)
+#undef MP_DECL
 
     // Record / replay / event logs (allocated only when enabled)
     mpenv_step_log *recordLog;             // [W] written by the step

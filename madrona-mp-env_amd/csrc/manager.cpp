@@ -20,6 +20,7 @@
 
 #include <dlfcn.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "engine.h"
@@ -47,10 +48,17 @@ int fail(int code, const std::string &msg)
         }                                                                                 \
     } while (0)
 
-// Order of TrainInterface inputs/outputs (mgr.cpp:2383-2431).
+// Order of TrainInterface inputs/outputs (mgr.cpp:2383-2431).  An output
+// with `direct` set is one gpuStreamStep has k_obs / k_lidar write straight
+// into the caller's buffer, through that member of OutTab (engine.h),
+// instead of copying it afterwards.  `zero` marks the agent maps: the step
+// never writes them and they stay all zeros, so their copy is a zero fill
+// (on the direct path k_lidar's, through the table).
 struct TIEntry {
     const char *name;
     int32_t id;
+    float *OutTab::*direct = nullptr;
+    bool zero = false;
 };
 const TIEntry kTIInputs[] = {
     { "discrete", MPENV_EXPORT_PVP_DISCRETE_ACTION },
@@ -60,23 +68,23 @@ const TIEntry kTIInputs[] = {
     { "pbt.policy_assignments", MPENV_EXPORT_AGENT_POLICY },
 };
 const TIEntry kTIOutputs[] = {
-    { "fwd_lidar", MPENV_EXPORT_FWD_LIDAR },
-    { "rear_lidar", MPENV_EXPORT_REAR_LIDAR },
+    { "fwd_lidar", MPENV_EXPORT_FWD_LIDAR, &OutTab::fwdLidar },
+    { "rear_lidar", MPENV_EXPORT_REAR_LIDAR, &OutTab::rearLidar },
     { "hp", MPENV_EXPORT_HP },
     { "magazine", MPENV_EXPORT_MAGAZINE },
     { "alive", MPENV_EXPORT_ALIVE },
-    { "self", MPENV_EXPORT_SELF_OBSERVATION },
-    { "filters_state", MPENV_EXPORT_FILTERS_STATE },
-    { "teammates", MPENV_EXPORT_TEAMMATE_OBSERVATIONS },
-    { "opponents", MPENV_EXPORT_OPPONENT_OBSERVATIONS },
+    { "self", MPENV_EXPORT_SELF_OBSERVATION, &OutTab::selfObs },
+    { "filters_state", MPENV_EXPORT_FILTERS_STATE, &OutTab::filters },
+    { "teammates", MPENV_EXPORT_TEAMMATE_OBSERVATIONS, &OutTab::tmObs },
+    { "opponents", MPENV_EXPORT_OPPONENT_OBSERVATIONS, &OutTab::oppObs },
     { "opponents_last_known", MPENV_EXPORT_OPPONENT_LAST_KNOWN_OBSERVATIONS },
-    { "self_pos", MPENV_EXPORT_SELF_POSITION },
-    { "teammate_positions", MPENV_EXPORT_TEAMMATE_POSITIONS },
-    { "opponent_positions", MPENV_EXPORT_OPPONENT_POSITIONS },
+    { "self_pos", MPENV_EXPORT_SELF_POSITION, &OutTab::selfPos },
+    { "teammate_positions", MPENV_EXPORT_TEAMMATE_POSITIONS, &OutTab::tmPos },
+    { "opponent_positions", MPENV_EXPORT_OPPONENT_POSITIONS, &OutTab::oppPos },
     { "opponent_last_known_positions", MPENV_EXPORT_OPPONENT_LAST_KNOWN_POSITIONS },
-    { "opponent_masks", MPENV_EXPORT_OPPONENT_MASKS },
-    { "agent_map", MPENV_EXPORT_AGENT_MAP },
-    { "unmasked_agent_map", MPENV_EXPORT_AGENT_MAP },
+    { "opponent_masks", MPENV_EXPORT_OPPONENT_MASKS, &OutTab::masks },
+    { "agent_map", MPENV_EXPORT_AGENT_MAP, &OutTab::agentMap0, true },
+    { "unmasked_agent_map", MPENV_EXPORT_AGENT_MAP, &OutTab::agentMap1, true },
     { "reward_coefs", MPENV_EXPORT_REWARD_HYPER_PARAMS },
     { "rewards", MPENV_EXPORT_REWARD },
     { "dones", MPENV_EXPORT_DONE },
@@ -437,84 +445,83 @@ struct mpenv_manager {
     }
 
     bool exportDesc(int32_t id, TensorDesc &d);
+    void *exportPtr(int32_t id);
     void gatherDebug(bool explore = false);
 };
 
-bool mpenv_manager::exportDesc(int32_t id, TensorDesc &d)
+template <typename T>
+constexpr int32_t dtypeOf()
 {
-    const int64_t A = S.A, W = S.W;
-    auto set = [&](void *p, int32_t dt, std::initializer_list<int64_t> dims) {
-        d.ptr = p;
+    static_assert(std::is_same<T, float>::value || std::is_same<T, int32_t>::value || std::is_same<T, uint32_t>::value,
+                  "no MPENV_DTYPE_* for this element type");
+    return std::is_same<T, float>::value ? MPENV_DTYPE_FLOAT32
+           : std::is_same<T, int32_t>::value ? MPENV_DTYPE_INT32
+                                             : MPENV_DTYPE_UINT32;
+}
+
+// dtype and dims of an export for W worlds of N agents: no manager, no GPU
+// (mpenv_export_layout).  The buffer table's exports, then the ones that
+// are not a plain view of a table buffer.
+static bool exportLayout(int32_t id, int64_t W, int64_t N, TensorDesc &d)
+{
+    const int64_t A = W * N;
+    auto set = [&](int32_t dt, std::initializer_list<int64_t> dims) {
         d.dtype = dt;
         d.dims.assign(dims.begin(), dims.end());
         return true;
     };
     switch (id) {
-    case MPENV_EXPORT_RESET: return set(S.reset, MPENV_DTYPE_INT32, { W, 1 });
-    case MPENV_EXPORT_WORLD_CURRICULUM: return set(S.worldCurr, MPENV_DTYPE_INT32, { W, 1 });
-    case MPENV_EXPORT_EXPLORE_ACTION: return set(S.exploreAction, MPENV_DTYPE_INT32, { A, 4 });
-    case MPENV_EXPORT_PVP_DISCRETE_ACTION: return set(S.discreteAction, MPENV_DTYPE_INT32, { A, 4 });
-    case MPENV_EXPORT_PVP_AIM_ACTION: return set(S.aimAction, MPENV_DTYPE_FLOAT32, { A, 1, 2 });
-    case MPENV_EXPORT_PVP_DISCRETE_AIM_ACTION: return set(S.discreteAim, MPENV_DTYPE_INT32, { A, 2 });
-    case MPENV_EXPORT_REWARD: return set(S.reward, MPENV_DTYPE_FLOAT32, { A, 1 });
-    case MPENV_EXPORT_DONE: return set(S.done, MPENV_DTYPE_INT32, { A, 1 });
-    case MPENV_EXPORT_MATCH_RESULT: return set(S.matchResult, MPENV_DTYPE_INT32, { W, 30 });
-    case MPENV_EXPORT_AGENT_POLICY: return set(S.policy, MPENV_DTYPE_INT32, { A, 1 });
-    case MPENV_EXPORT_SELF_OBSERVATION: return set(S.selfObs, MPENV_DTYPE_FLOAT32, { A, kSelfObs });
-    case MPENV_EXPORT_TEAMMATE_OBSERVATIONS: return set(S.tmObs, MPENV_DTYPE_FLOAT32, { A, 5, kOtherObs });
-    case MPENV_EXPORT_OPPONENT_OBSERVATIONS: return set(S.oppObs, MPENV_DTYPE_FLOAT32, { A, 6, kOtherObs });
-    case MPENV_EXPORT_OPPONENT_LAST_KNOWN_OBSERVATIONS: return set(S.lkObs, MPENV_DTYPE_FLOAT32, { A, 6, kOtherObs });
-    case MPENV_EXPORT_SELF_POSITION: return set(S.selfPos, MPENV_DTYPE_FLOAT32, { A, 3 });
-    case MPENV_EXPORT_TEAMMATE_POSITIONS: return set(S.tmPos, MPENV_DTYPE_FLOAT32, { A, 5, 3 });
-    case MPENV_EXPORT_OPPONENT_POSITIONS: return set(S.oppPos, MPENV_DTYPE_FLOAT32, { A, 6, 3 });
-    case MPENV_EXPORT_OPPONENT_LAST_KNOWN_POSITIONS: return set(S.lkPos, MPENV_DTYPE_FLOAT32, { A, 6, 3 });
-    case MPENV_EXPORT_OPPONENT_MASKS: return set(S.masks, MPENV_DTYPE_FLOAT32, { A, 6, 1 });
-    case MPENV_EXPORT_FWD_LIDAR: return set(S.fwdLidar, MPENV_DTYPE_FLOAT32, { A, 2, 32, 4 });
-    case MPENV_EXPORT_REAR_LIDAR: return set(S.rearLidar, MPENV_DTYPE_FLOAT32, { A, 2, 8, 4 });
-    case MPENV_EXPORT_AGENT_MAP:
-    case MPENV_EXPORT_UNMASKED_AGENT_MAP: return set(S.agentMap, MPENV_DTYPE_FLOAT32, { A, 16, 16, 4 });
-    case MPENV_EXPORT_HP: return set(S.hp, MPENV_DTYPE_FLOAT32, { A, 1 });
-    case MPENV_EXPORT_ALIVE: return set(S.alive, MPENV_DTYPE_FLOAT32, { A, 1 });
-    case MPENV_EXPORT_MAGAZINE: return set(S.magazine, MPENV_DTYPE_INT32, { A, 2 });
-    case MPENV_EXPORT_FULL_TEAM_ACTIONS: return set(S.ftActions, MPENV_DTYPE_INT32, { W * 2, 6, 4 });
-    case MPENV_EXPORT_FULL_TEAM_GLOBAL: return set(S.ftGlobal, MPENV_DTYPE_FLOAT32, { W * 2, MPENV_FT_GLOBAL_DIM });
-    case MPENV_EXPORT_FULL_TEAM_PLAYERS:
-        return set(S.ftPlayers, MPENV_DTYPE_FLOAT32, { W * 2, 6, MPENV_FT_PLAYER_DIM });
-    case MPENV_EXPORT_FULL_TEAM_ENEMIES:
-        return set(S.ftEnemies, MPENV_DTYPE_FLOAT32, { W * 2, 6, MPENV_FT_ENEMY_DIM });
-    case MPENV_EXPORT_FULL_TEAM_LAST_KNOWN_ENEMIES:
-        return set(S.ftLastKnown, MPENV_DTYPE_FLOAT32, { W * 2, 6, MPENV_FT_COMMON_DIM });
-    case MPENV_EXPORT_FULL_TEAM_FWD_LIDAR: return set(S.ftFwdLidar, MPENV_DTYPE_FLOAT32, { W * 2, 6, 2, 32, 4 });
-    case MPENV_EXPORT_FULL_TEAM_REAR_LIDAR: return set(S.ftRearLidar, MPENV_DTYPE_FLOAT32, { W * 2, 6, 2, 8, 4 });
-    case MPENV_EXPORT_FULL_TEAM_REWARD: return set(S.ftReward, MPENV_DTYPE_FLOAT32, { W * 2, 1 });
-    case MPENV_EXPORT_FULL_TEAM_DONE: return set(S.ftDone, MPENV_DTYPE_INT32, { W * 2, 1 });
-    case MPENV_EXPORT_FULL_TEAM_POLICY_ASSIGNMENTS: return set(S.ftPolicy, MPENV_DTYPE_INT32, { W * 2, 1 });
-    case MPENV_EXPORT_FILTERS_STATE: return set(S.filters, MPENV_DTYPE_FLOAT32, { A, 1 });
-    case MPENV_EXPORT_REWARD_HYPER_PARAMS: return set(S.rewardCoefs, MPENV_DTYPE_FLOAT32, { A, 9 });
-    case MPENV_EXPORT_EVENT_LOG:
-        if (!S.events) return false;
-        return set(S.events, MPENV_DTYPE_INT32, { W, S.evStride, 6 });
-    case MPENV_EXPORT_PACKED_STEP_SNAPSHOT:
-        if (!S.snapshots) return false;
-        return set(S.snapshots, MPENV_DTYPE_INT32, { W, 48 });
+#define MP_LAYOUT(n, type, kind, eid, ...) \
+    case eid: return set(dtypeOf<type>(), { bufRows(kind, W, N), __VA_ARGS__ });
+        MP_BUFS(MP_BUF_SKIP, MP_LAYOUT)
+#undef MP_LAYOUT
+    case MPENV_EXPORT_UNMASKED_AGENT_MAP: return exportLayout(MPENV_EXPORT_AGENT_MAP, W, N, d);
+    case MPENV_EXPORT_EVENT_LOG: return set(MPENV_DTYPE_INT32, { W, 2 * N + 1, 6 });
+    case MPENV_EXPORT_PACKED_STEP_SNAPSHOT: return set(MPENV_DTYPE_INT32, { W, 48 });
     case MPENV_EXPORT_RECORD_LOG:
-        if (!S.recordLog) return false;
-        return set(S.recordLog, MPENV_DTYPE_INT32, { W, 217 });
-    case MPENV_EXPORT_REPLAY_LOG:
-        if (!S.replayLog) return false;
-        return set((void *)S.replayLog, MPENV_DTYPE_INT32, { W, 217 });
-    case MPENV_EXPORT_SNAPSHOT_WRITTEN:
-        if (!S.snapshots) return false;
-        return set(S.snapWritten, MPENV_DTYPE_INT32, { W, 1 });
-    case MPENV_EXPORT_SIM_CONTROL: return set(S.trainCtrl, MPENV_DTYPE_INT32, { 3 });
-    case MPENV_EXPORT_DEBUG_AGENT_F32: gatherDebug(); return set(dbgAF, MPENV_DTYPE_FLOAT32, { A, MPENV_DBG_AF_COUNT });
-    case MPENV_EXPORT_DEBUG_AGENT_I32: gatherDebug(); return set(dbgAI, MPENV_DTYPE_INT32, { A, MPENV_DBG_AI_COUNT });
-    case MPENV_EXPORT_DEBUG_WORLD_I32: gatherDebug(); return set(dbgWI, MPENV_DTYPE_INT32, { W, MPENV_DBG_WI_COUNT });
-    case MPENV_EXPORT_DEBUG_WORLD_F32: gatherDebug(); return set(dbgWF, MPENV_DTYPE_FLOAT32, { W, MPENV_DBG_WF_COUNT });
-    case MPENV_EXPORT_DEBUG_EXPLORE: gatherDebug(true); return set(dbgExplore, MPENV_DTYPE_UINT32, { A, kGridCells });
-    case MPENV_EXPORT_DEBUG_CRUMBS: gatherDebug(); return set(dbgCrumbs, MPENV_DTYPE_FLOAT32, { W, kMaxCrumbs, 8 });
+    case MPENV_EXPORT_REPLAY_LOG: return set(MPENV_DTYPE_INT32, { W, 217 });
+    case MPENV_EXPORT_SNAPSHOT_WRITTEN: return set(MPENV_DTYPE_INT32, { W, 1 });
+    case MPENV_EXPORT_SIM_CONTROL: return set(MPENV_DTYPE_INT32, { 3 });
+    case MPENV_EXPORT_DEBUG_AGENT_F32: return set(MPENV_DTYPE_FLOAT32, { A, MPENV_DBG_AF_COUNT });
+    case MPENV_EXPORT_DEBUG_AGENT_I32: return set(MPENV_DTYPE_INT32, { A, MPENV_DBG_AI_COUNT });
+    case MPENV_EXPORT_DEBUG_WORLD_I32: return set(MPENV_DTYPE_INT32, { W, MPENV_DBG_WI_COUNT });
+    case MPENV_EXPORT_DEBUG_WORLD_F32: return set(MPENV_DTYPE_FLOAT32, { W, MPENV_DBG_WF_COUNT });
+    case MPENV_EXPORT_DEBUG_EXPLORE: return set(MPENV_DTYPE_UINT32, { A, kGridCells });
+    case MPENV_EXPORT_DEBUG_CRUMBS: return set(MPENV_DTYPE_FLOAT32, { W, kMaxCrumbs, 8 });
     default: return false;
     }
+}
+
+// The buffer behind an export; null for a log buffer that is not allocated.
+void *mpenv_manager::exportPtr(int32_t id)
+{
+    switch (id) {
+#define MP_PTR(n, type, kind, eid, ...) \
+    case eid: return S.n;
+        MP_BUFS(MP_BUF_SKIP, MP_PTR)
+#undef MP_PTR
+    case MPENV_EXPORT_UNMASKED_AGENT_MAP: return S.agentMap;
+    case MPENV_EXPORT_EVENT_LOG: return S.events;
+    case MPENV_EXPORT_PACKED_STEP_SNAPSHOT: return S.snapshots;
+    case MPENV_EXPORT_RECORD_LOG: return S.recordLog;
+    case MPENV_EXPORT_REPLAY_LOG: return const_cast<mpenv_step_log *>(S.replayLog);
+    case MPENV_EXPORT_SNAPSHOT_WRITTEN: return S.snapshots ? S.snapWritten : nullptr;
+    case MPENV_EXPORT_SIM_CONTROL: return S.trainCtrl;
+    case MPENV_EXPORT_DEBUG_AGENT_F32: gatherDebug(); return dbgAF;
+    case MPENV_EXPORT_DEBUG_AGENT_I32: gatherDebug(); return dbgAI;
+    case MPENV_EXPORT_DEBUG_WORLD_I32: gatherDebug(); return dbgWI;
+    case MPENV_EXPORT_DEBUG_WORLD_F32: gatherDebug(); return dbgWF;
+    case MPENV_EXPORT_DEBUG_EXPLORE: gatherDebug(true); return dbgExplore;
+    case MPENV_EXPORT_DEBUG_CRUMBS: gatherDebug(); return dbgCrumbs;
+    default: return nullptr;
+    }
+}
+
+bool mpenv_manager::exportDesc(int32_t id, TensorDesc &d)
+{
+    if (!exportLayout(id, S.W, S.N, d)) return false;
+    d.ptr = exportPtr(id);
+    return d.ptr != nullptr;
 }
 
 void mpenv_manager::gatherDebug(bool explore)
@@ -746,62 +753,34 @@ static void allocState(mpenv_manager &m)
 #undef MP_ALLOC_AI
 #undef MP_ALLOC_WI
 #undef MP_ALLOC_WF
+    // T and trackLen: the run-time row shapes of the buffer table (engine.h)
+    const int64_t T = S.T, trackLen = m.sc.spawnTrackLen;
+#define MP_ALLOC(n, type, kind, ...) S.n = m.alloc<type>((size_t)(bufRows(kind, S.W, S.N) * rowElems(__VA_ARGS__)));
+#define MP_ALLOC_E(n, type, kind, id, ...) MP_ALLOC(n, type, kind, __VA_ARGS__)
     S.dmg = m.alloc<float>(A * kMaxTeamSize);
     S.dmgStride = (int64_t)A;
-    S.visMask = m.alloc<uint8_t>(A);
+    MP_BUFS_A(MP_ALLOC, MP_ALLOC_E)
     m.wireErr = m.alloc<uint32_t>(1);
     HIP_CHECK(hipMemsetAsync(m.wireErr, 0, sizeof(uint32_t), m.stream));
     m.outTabDev = m.alloc<OutTab>(1); // zeros: off
     S.outTab = m.outTabDev;
     m.wireEp = m.alloc<int32_t>(2 * W);
     HIP_CHECK(hipMemsetAsync(m.wireEp, 0, sizeof(int32_t) * 2 * W, m.stream));
-    S.visOcc = m.alloc<uint16_t>((size_t)A * S.T * 4);
-    HIP_CHECK(hipMemsetAsync(S.visOcc, 0xff, sizeof(uint16_t) * (size_t)A * S.T * 4, m.stream));
-    S.exploreBits = m.alloc<uint64_t>(A * kExploreTiles);
-    S.filtLast = m.alloc<int32_t>(W * 6);
-    S.zoneStats = m.alloc<int32_t>(W * 25);
+    MP_BUFS_B(MP_ALLOC, MP_ALLOC_E)
+    HIP_CHECK(hipMemsetAsync(S.visOcc, 0xff, sizeof(uint16_t) * A * T * 4, m.stream)); // hints: none
     S.resetKeys = m.alloc<mp::RandKey>(A * 11);
-    S.spawnTrack = m.alloc<uint32_t>(W * 3 * (size_t)m.sc.spawnTrackLen);
-    S.crumbs = m.alloc<float4>(W * kMaxCrumbs * 2);
-    S.reset = m.alloc<int32_t>(W);
-    S.worldCurr = m.alloc<int32_t>(W);
-    S.matchResult = m.alloc<int32_t>(W * 30);
-    S.exploreAction = m.alloc<int32_t>(A * 4);
-    S.discreteAction = m.alloc<int32_t>(A * 4);
-    S.aimAction = m.alloc<float>(A * 2);
-    S.discreteAim = m.alloc<int32_t>(A * 2);
-    S.policy = m.alloc<int32_t>(A);
-    S.botAction = m.alloc<int32_t>(A * 7);
-    S.reward = m.alloc<float>(A);
-    S.done = m.alloc<int32_t>(A);
-    S.selfObs = m.alloc<float>(A * kSelfObs);
-    S.filters = m.alloc<float>(A);
-    S.tmObs = m.alloc<float>(A * 5 * kOtherObs);
-    S.oppObs = m.alloc<float>(A * 6 * kOtherObs);
-    S.lkObs = m.alloc<float>(A * 6 * kOtherObs);
-    S.selfPos = m.alloc<float>(A * 3);
-    S.tmPos = m.alloc<float>(A * 15);
-    S.oppPos = m.alloc<float>(A * 18);
-    S.lkPos = m.alloc<float>(A * 18);
-    S.masks = m.alloc<float>(A * 6);
-    S.fwdLidar = m.alloc<float>(A * kFwdRays * 4);
-    S.rearLidar = m.alloc<float>(A * kRearRays * 4);
-    S.agentMap = m.alloc<float>(A * 16 * 16 * 4);
-    S.hp = m.alloc<float>(A);
-    S.alive = m.alloc<float>(A);
-    S.magazine = m.alloc<int32_t>(A * 2);
-    S.rewardCoefs = m.alloc<float>(A * 9);
-    S.trainCtrl = m.alloc<int32_t>(3);
-    S.ftActions = m.alloc<int32_t>(W * 2 * 6 * 4);
-    S.ftGlobal = m.alloc<float>(W * 2 * MPENV_FT_GLOBAL_DIM);
-    S.ftPlayers = m.alloc<float>(W * 2 * 6 * MPENV_FT_PLAYER_DIM);
-    S.ftEnemies = m.alloc<float>(W * 2 * 6 * MPENV_FT_ENEMY_DIM);
-    S.ftLastKnown = m.alloc<float>(W * 2 * 6 * MPENV_FT_COMMON_DIM);
-    S.ftFwdLidar = m.alloc<float>(W * 2 * 6 * kFwdRays * 4);
-    S.ftRearLidar = m.alloc<float>(W * 2 * 6 * kRearRays * 4);
-    S.ftReward = m.alloc<float>(W * 2);
-    S.ftDone = m.alloc<int32_t>(W * 2);
-    S.ftPolicy = m.alloc<int32_t>(W * 2);
+    MP_BUFS_C(MP_ALLOC, MP_ALLOC_E)
+#undef MP_ALLOC
+#undef MP_ALLOC_E
+    // a buffer the lists above missed would be a null pointer in a kernel
+#define MP_NAMED(n, ...) { #n, S.n },
+    const struct {
+        const char *name;
+        const void *ptr;
+    } bufs[] = { MP_BUFS(MP_NAMED, MP_NAMED) { "dmg", S.dmg }, { "resetKeys", S.resetKeys } };
+#undef MP_NAMED
+    for (const auto &b : bufs)
+        if (!b.ptr) throw std::runtime_error(std::string("device buffer ") + b.name + " was not allocated");
 }
 
 static void openLogs(mpenv_manager &m, const mpenv_config *cfg)
@@ -841,8 +820,7 @@ static void openLogs(mpenv_manager &m, const mpenv_config *cfg)
 // to its size, and the scene's world-id offset advanced so RNG keys stay
 // global.  Worlds never read each other, so step kernels launched on
 // different ranges are independent and can run on concurrent streams.
-static void sliceState(const DevState &S, const SceneDev &sc, int64_t w0, int64_t nw, int32_t track_len,
-                       DevState &G, SceneDev &gsc)
+static void sliceState(const DevState &S, const SceneDev &sc, int64_t w0, int64_t nw, DevState &G, SceneDev &gsc)
 {
     G = S;
     gsc = sc;
@@ -858,54 +836,15 @@ static void sliceState(const DevState &S, const SceneDev &sc, int64_t w0, int64_
     MP_WORLD_F32(MP_SL_W)
 #undef MP_SL_A
 #undef MP_SL_W
+    const int64_t T = S.T, trackLen = sc.spawnTrackLen; // the buffer table's run-time row shapes
+#define MP_SL(n, type, kind, ...) G.n = S.n + bufFirstRow(kind, w0, S.N) * rowElems(__VA_ARGS__);
+#define MP_SL_E(n, type, kind, id, ...) MP_SL(n, type, kind, __VA_ARGS__)
+    MP_BUFS(MP_SL, MP_SL_E)
+#undef MP_SL
+#undef MP_SL_E
     G.outBase = S.outBase + g0;
     G.dmg = S.dmg + g0; // stride stays S.dmgStride
-    G.visMask = S.visMask + g0;
-    G.visOcc = S.visOcc + g0 * S.T * 4;
-    G.exploreBits = S.exploreBits + g0 * kExploreTiles;
-    G.filtLast = S.filtLast + w0 * 6;
     G.resetKeys = S.resetKeys + g0 * 11;
-    G.zoneStats = S.zoneStats + w0 * 25;
-    G.spawnTrack = S.spawnTrack + w0 * 3 * track_len;
-    G.crumbs = S.crumbs + w0 * kMaxCrumbs * 2;
-    G.reset = S.reset + w0;
-    G.worldCurr = S.worldCurr + w0;
-    G.matchResult = S.matchResult + w0 * 30;
-    G.exploreAction = S.exploreAction + g0 * 4;
-    G.discreteAction = S.discreteAction + g0 * 4;
-    G.aimAction = S.aimAction + g0 * 2;
-    G.discreteAim = S.discreteAim + g0 * 2;
-    G.policy = S.policy + g0;
-    G.botAction = S.botAction + g0 * 7;
-    G.reward = S.reward + g0;
-    G.done = S.done + g0;
-    G.selfObs = S.selfObs + g0 * kSelfObs;
-    G.filters = S.filters + g0;
-    G.tmObs = S.tmObs + g0 * 5 * kOtherObs;
-    G.oppObs = S.oppObs + g0 * 6 * kOtherObs;
-    G.lkObs = S.lkObs + g0 * 6 * kOtherObs;
-    G.selfPos = S.selfPos + g0 * 3;
-    G.tmPos = S.tmPos + g0 * 15;
-    G.oppPos = S.oppPos + g0 * 18;
-    G.lkPos = S.lkPos + g0 * 18;
-    G.masks = S.masks + g0 * 6;
-    G.fwdLidar = S.fwdLidar + g0 * kFwdRays * 4;
-    G.rearLidar = S.rearLidar + g0 * kRearRays * 4;
-    G.agentMap = S.agentMap + g0 * 16 * 16 * 4;
-    G.hp = S.hp + g0;
-    G.alive = S.alive + g0;
-    G.magazine = S.magazine + g0 * 2;
-    G.rewardCoefs = S.rewardCoefs + g0 * 9;
-    G.ftActions = S.ftActions + w0 * 2 * 6 * 4;
-    G.ftGlobal = S.ftGlobal + w0 * 2 * MPENV_FT_GLOBAL_DIM;
-    G.ftPlayers = S.ftPlayers + w0 * 2 * 6 * MPENV_FT_PLAYER_DIM;
-    G.ftEnemies = S.ftEnemies + w0 * 2 * 6 * MPENV_FT_ENEMY_DIM;
-    G.ftLastKnown = S.ftLastKnown + w0 * 2 * 6 * MPENV_FT_COMMON_DIM;
-    G.ftFwdLidar = S.ftFwdLidar + w0 * 2 * 6 * kFwdRays * 4;
-    G.ftRearLidar = S.ftRearLidar + w0 * 2 * 6 * kRearRays * 4;
-    G.ftReward = S.ftReward + w0 * 2;
-    G.ftDone = S.ftDone + w0 * 2;
-    G.ftPolicy = S.ftPolicy + w0 * 2;
     if (S.recordLog) G.recordLog = S.recordLog + w0;
     if (S.replayLog) G.replayLog = S.replayLog + w0;
     if (S.events) G.events = S.events + w0 * S.evStride;
@@ -935,7 +874,7 @@ void mpenv_manager::setupGroups(int want)
         const int64_t w0 = (int64_t)S.W * i / groups, w1 = (int64_t)S.W * (i + 1) / groups;
         DevState G;
         SceneDev gs;
-        sliceState(S, sc, w0, w1 - w0, sc.spawnTrackLen, G, gs);
+        sliceState(S, sc, w0, w1 - w0, G, gs);
         gS.push_back(G);
         gsc.push_back(gs);
         hipStream_t st;
@@ -1118,6 +1057,21 @@ int mpenv_export_tensor(mpenv_manager *m, int32_t id, void **ptr, int32_t *dtype
     return MPENV_OK;
 }
 
+int mpenv_export_layout(int32_t id, uint32_t num_worlds, uint32_t team_size, int32_t *dtype, int32_t *ndim,
+                        int64_t *dims)
+{
+    if (!dtype || !ndim || !dims) return fail(MPENV_ERR_INVALID, "null argument");
+    if (num_worlds == 0 || team_size == 0 || team_size > (uint32_t)kMaxTeamSize)
+        return fail(MPENV_ERR_INVALID, "num_worlds must be >= 1 and team_size in [1, 6]");
+    TensorDesc d;
+    if (!exportLayout(id, num_worlds, 2 * (int64_t)team_size, d))
+        return fail(MPENV_ERR_INVALID, "unknown export id " + std::to_string(id));
+    *dtype = d.dtype;
+    *ndim = (int32_t)d.dims.size();
+    for (size_t k = 0; k < d.dims.size(); k++) dims[k] = d.dims[k];
+    return MPENV_OK;
+}
+
 int mpenv_train_interface_size(int32_t *num_inputs, int32_t *num_outputs)
 {
     if (num_inputs) *num_inputs = kNumTIInputs;
@@ -1140,59 +1094,32 @@ int mpenv_train_interface_entry(int32_t is_output, int32_t idx, const char **nam
 // them, as one batched copy launch (the agent maps are never written by the
 // step and stay all zeros, so their copies are zero fills); a segment whose
 // pointers are not 16-B aligned falls back to hipMemcpyAsync.
-// zeros: 1 = only the agent maps' zero fills, 0 or -2 = the other outputs
-// only, -1 = every output.
-// The outputs gpuStreamStep has k_obs / k_lidar write straight into the
-// caller's buffers (engine.h OutTab) instead of copying them afterwards.
-static bool directOutput(int32_t id)
-{
-    switch (id) {
-    case MPENV_EXPORT_OPPONENT_MASKS: case MPENV_EXPORT_FILTERS_STATE: case MPENV_EXPORT_SELF_OBSERVATION:
-    case MPENV_EXPORT_SELF_POSITION: case MPENV_EXPORT_TEAMMATE_OBSERVATIONS:
-    case MPENV_EXPORT_TEAMMATE_POSITIONS: case MPENV_EXPORT_OPPONENT_OBSERVATIONS:
-    case MPENV_EXPORT_OPPONENT_POSITIONS: case MPENV_EXPORT_FWD_LIDAR: case MPENV_EXPORT_REAR_LIDAR:
-        return true;
-    default:
-        return false;
-    }
-}
+// `what` selects the segments.
+enum TISel : unsigned {
+    kSelInputs = 1, // every input, caller -> engine
+    kSelState = 2,  // the outputs that are only ever copied (hp, rewards, last-known rows, ...)
+    kSelDirect = 4, // the outputs an OutTab can take instead (TIEntry::direct)
+    kSelZeros = 8,  // the agent maps' zero fills
+};
 
-// The call's OutTab, or false when some direct output's buffer is missing
-// or not 16-B aligned (the kernels store float4 rows): then every output is
+// The call's OutTab: every output with TIEntry::direct set written straight
+// into the caller's buffer; or false when one of those buffers is missing or
+// not 16-B aligned (the kernels store float4 rows): then every output is
 // copied as before.
 static bool directTable(void **buffers, OutTab &t)
 {
     t = OutTab {};
     t.on = 1;
-    int maps = 0;
     for (int i = 0; i < kNumTIOutputs; i++) {
-        const int32_t id = kTIOutputs[i].id;
-        if (!directOutput(id) && id != MPENV_EXPORT_AGENT_MAP) continue;
+        if (!kTIOutputs[i].direct) continue;
         float *p = static_cast<float *>(buffers[kNumTIInputs + i]);
         if (!p || ((uintptr_t)p & 15u)) return false;
-        if (id == MPENV_EXPORT_AGENT_MAP) {
-            (maps++ == 0 ? t.agentMap0 : t.agentMap1) = p;
-            continue;
-        }
-        switch (id) {
-        case MPENV_EXPORT_OPPONENT_MASKS: t.masks = p; break;
-        case MPENV_EXPORT_FILTERS_STATE: t.filters = p; break;
-        case MPENV_EXPORT_SELF_OBSERVATION: t.selfObs = p; break;
-        case MPENV_EXPORT_SELF_POSITION: t.selfPos = p; break;
-        case MPENV_EXPORT_TEAMMATE_OBSERVATIONS: t.tmObs = p; break;
-        case MPENV_EXPORT_TEAMMATE_POSITIONS: t.tmPos = p; break;
-        case MPENV_EXPORT_OPPONENT_OBSERVATIONS: t.oppObs = p; break;
-        case MPENV_EXPORT_OPPONENT_POSITIONS: t.oppPos = p; break;
-        case MPENV_EXPORT_FWD_LIDAR: t.fwdLidar = p; break;
-        case MPENV_EXPORT_REAR_LIDAR: t.rearLidar = p; break;
-        default: break;
-        }
+        t.*kTIOutputs[i].direct = p;
     }
-    return maps == 2;
+    return true;
 }
 
-static int copyTI(mpenv_manager *m, hipStream_t st, void **buffers, bool inputs, bool outputs, int zeros = -1,
-                  bool skip_direct = false, const OutTab *tab = nullptr)
+static int copyTI(mpenv_manager *m, hipStream_t st, void **buffers, unsigned what, const OutTab *tab = nullptr)
 {
     CopyBatch b {};
     if (tab) { // the out table rides the first copy launch (engine.h CopyBatch)
@@ -1214,19 +1141,17 @@ static int copyTI(mpenv_manager *m, hipStream_t st, void **buffers, bool inputs,
     };
     int k = 0;
     for (int i = 0; i < kNumTIInputs; i++, k++) {
-        if (!inputs || !buffers[k]) continue;
+        if (!(what & kSelInputs) || !buffers[k]) continue;
         TensorDesc d;
         m->exportDesc(kTIInputs[i].id, d);
         add(buffers[k], d.ptr, d.bytes());
     }
     for (int i = 0; i < kNumTIOutputs; i++, k++) {
-        if (!outputs || !buffers[k]) continue;
-        const bool zero = kTIOutputs[i].id == MPENV_EXPORT_AGENT_MAP;
-        if ((zeros == 1 && !zero) || ((zeros == 0 || zeros == -2) && zero)) continue;
-        if (skip_direct && directOutput(kTIOutputs[i].id)) continue;
+        const TIEntry &e = kTIOutputs[i];
+        if (!(what & (e.zero ? kSelZeros : e.direct ? kSelDirect : kSelState)) || !buffers[k]) continue;
         TensorDesc d;
-        m->exportDesc(kTIOutputs[i].id, d);
-        add(zero ? nullptr : d.ptr, buffers[k], d.bytes());
+        m->exportDesc(e.id, d);
+        add(e.zero ? nullptr : d.ptr, buffers[k], d.bytes());
     }
     if ((b.n > 0 || b.tabDst) && launchCopyBatch(b, st)) throw std::runtime_error("copy launch failed");
     return 0;
@@ -1250,7 +1175,7 @@ int mpenv_gpu_stream_init(mpenv_manager *m, void *stream, void **buffers)
         ensureZStream(m);
         hipStream_t st = stream ? (hipStream_t)stream : m->stream;
         m->runInitGraph(st);
-        copyTI(m, st, buffers, false, true);
+        copyTI(m, st, buffers, kSelState | kSelDirect | kSelZeros);
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
     }
@@ -1277,13 +1202,13 @@ int mpenv_gpu_stream_step(mpenv_manager *m, void *stream, void **buffers)
             // beside the step, ordered after whatever the caller queued
             HIP_CHECK(hipEventRecord(m->zForkEv, st));
             HIP_CHECK(hipStreamWaitEvent(m->zStream, m->zForkEv, 0));
-            copyTI(m, m->zStream, buffers, false, true, 1);
+            copyTI(m, m->zStream, buffers, kSelZeros);
             HIP_CHECK(hipEventRecord(m->zJoinEv, m->zStream));
         }
         const OutTab off {};
-        copyTI(m, st, buffers, true, false, -1, false, direct ? &tab : nullptr); // sets the table
+        copyTI(m, st, buffers, kSelInputs, direct ? &tab : nullptr); // sets the table
         m->runStep(st);
-        copyTI(m, st, buffers, false, true, 0, direct, direct ? &off : nullptr); // clears it
+        copyTI(m, st, buffers, direct ? kSelState : kSelState | kSelDirect, direct ? &off : nullptr); // clears it
         if (!direct) HIP_CHECK(hipStreamWaitEvent(st, m->zJoinEv, 0));
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());

@@ -96,15 +96,15 @@ __host__ __device__ inline WireLayout wireLayout(int64_t A, int64_t W, bool keyf
     L.mag = take(A * 8);
     L.packed = take(A * 4);
     L.vis = take(A);
-    L.coefs = take(A * 36);
+    L.coefs = take(A * row::rewardCoefs * 4);
     L.depth = take(A * kLidarRays * 4);
     const int64_t words = (A * kLidarRays + 31) / 32;
     L.plane[0] = take(words * 4);
     L.plane[1] = take(words * 4);
     for (int k = 0; k < kWireWI; k++) L.wi[k] = take(W * 4);
-    L.match = take(W * 120);
+    L.match = take(W * row::matchResult * 4);
     L.lkObs = keyframe ? take(A * 6 * kOtherObs * 4) : -1;
-    L.lkPos = keyframe ? take(A * 18 * 4) : -1;
+    L.lkPos = keyframe ? take(A * row::lkPos * 4) : -1;
     L.total = off;
     return L;
 }
@@ -131,7 +131,7 @@ __host__ __device__ inline WirePackGrid wirePackGrid(int64_t A, int64_t W)
     G.agents = blocks(A * kLidarRays);
     G.worlds = G.agents + blocks(A);
     G.match = G.worlds + blocks(W);
-    G.total = G.match + blocks((W * 120 + 15) / 16);
+    G.total = G.match + blocks((W * row::matchResult * 4 + 15) / 16);
     return G;
 }
 
@@ -206,7 +206,8 @@ __global__ void __launch_bounds__(256) k_wire_pack(DevState S, char *dst, WireLa
             const float4 *src = reinterpret_cast<const float4 *>(S.lkObs + g * 6 * kOtherObs);
             float4 *o = reinterpret_cast<float4 *>(dst + L.lkObs) + g * 6 * kOtherObs / 4;
             for (int q = 0; q < 6 * kOtherObs / 4; q++) o[q] = src[q];
-            for (int q = 0; q < 18; q++) reinterpret_cast<float *>(dst + L.lkPos)[g * 18 + q] = S.lkPos[g * 18 + q];
+            for (int q = 0; q < row::lkPos; q++)
+                reinterpret_cast<float *>(dst + L.lkPos)[g * row::lkPos + q] = S.lkPos[g * row::lkPos + q];
         }
         if (!fits) atomicOr(hflags, kWireOverflow);
     } else if (b < G.match) {
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(256) k_wire_pack(DevState S, char *dst, WireLa
         for (k = 0; k < kWireWI; k++) reinterpret_cast<int32_t *>(dst + L.wi[k])[w] = wv[k];
     } else {
         const int64_t i = (int64_t)(b - G.match) * 256 + threadIdx.x;
-        const int64_t bytes = S.W * 120;
+        const int64_t bytes = S.W * row::matchResult * 4;
         if (i * 16 >= bytes) return;
         if (i * 16 + 16 <= bytes) {
             reinterpret_cast<uint4 *>(dst + L.match)[i] = reinterpret_cast<const uint4 *>(S.matchResult)[i];
@@ -294,7 +295,7 @@ __host__ __device__ inline WireUnpackGrid wireUnpackGrid(int64_t A, int64_t W)
     G.agents = (uint32_t)((A * kLidarRays + 1023) / 1024);
     G.worlds = G.agents + blocks(A);
     G.match = G.worlds + blocks(W);
-    G.total = G.match + blocks((W * 120 + 15) / 16);
+    G.total = G.match + blocks((W * row::matchResult * 4 + 15) / 16);
     return G;
 }
 
@@ -357,7 +358,8 @@ __global__ void __launch_bounds__(256) k_wire_unpack(DevState S, const char *src
             const float4 *s4 = reinterpret_cast<const float4 *>(src + L.lkObs) + g * 6 * kOtherObs / 4;
             float4 *lk = reinterpret_cast<float4 *>(S.lkObs + g * 6 * kOtherObs);
             for (int q = 0; q < 6 * kOtherObs / 4; q++) lk[q] = s4[q];
-            for (int q = 0; q < 18; q++) S.lkPos[g * 18 + q] = reinterpret_cast<const float *>(src + L.lkPos)[g * 18 + q];
+            for (int q = 0; q < row::lkPos; q++)
+                S.lkPos[g * row::lkPos + q] = reinterpret_cast<const float *>(src + L.lkPos)[g * row::lkPos + q];
         }
     } else if (b < G.match) {
         const int64_t w = (int64_t)(b - G.worlds) * 256 + threadIdx.x;
@@ -367,7 +369,7 @@ __global__ void __launch_bounds__(256) k_wire_unpack(DevState S, const char *src
         // [W][30] i32 episode results: 16-B pieces of the flat array (both
         // ends 256-B aligned; the last piece may be partial)
         const int64_t i = (int64_t)(b - G.match) * 256 + threadIdx.x;
-        const int64_t bytes = S.W * 120;
+        const int64_t bytes = S.W * row::matchResult * 4;
         if (i * 16 >= bytes) return;
         if (i * 16 + 16 <= bytes) {
             reinterpret_cast<uint4 *>(S.matchResult)[i] = reinterpret_cast<const uint4 *>(src + L.match)[i];

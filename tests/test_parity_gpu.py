@@ -846,13 +846,18 @@ def test_step_graph_replay_equals_direct_launches(monkeypatch):
         T.compare(g.get(n), ref.get(n), f"{n} graph vs direct after an async re-capture")
 
 
-def test_logs_record_and_events_match_oracle(tmp_path):
+@pytest.mark.parametrize("groups", [1, 3])
+def test_logs_record_and_events_match_oracle(tmp_path, groups):
     """record_log_path + event_log_path: the engine's StepLog file,
     events.bin and steps.bin equal, byte for byte, what the oracle's buffers
-    give for the same run (mgr.cpp:104-116, sim.cpp:23-106, 4750-4792)."""
+    give for the same run (mgr.cpp:104-116, sim.cpp:23-106, 4750-4792).
+    With 3 world groups (four worlds each) every group writes its own slice
+    of the log buffers (manager.cpp sliceState)."""
     W, ts, steps = 12, 3, 250
     rec = str(tmp_path / "rec.bin")
     e = T.Engine(W, ts, sim_flags=1, record=rec, events=str(tmp_path))
+    if groups > 1:
+        e.set_world_groups(groups)
     o = T.Oracle(W, ts, sim_flags=1)
     o.lib.oracle_set_log_modes(o.h, 1, 0, 1)
     for sim in (e, o):
