@@ -304,6 +304,10 @@ static_assert(sizeof(mpenv_packed_step_snapshot) == 192, "PackedStepSnapshot lay
 #define MPENV_DTYPE_INT32 0
 #define MPENV_DTYPE_FLOAT32 1
 #define MPENV_DTYPE_UINT32 2
+/* snapshot sections only (mpenv_state_section_dtype); no export has them */
+#define MPENV_DTYPE_UINT8 3
+#define MPENV_DTYPE_UINT16 4
+#define MPENV_DTYPE_UINT64 5
 
 typedef struct mpenv_config {
     int32_t exec_mode;          /* MPENV_EXEC_* */
@@ -455,6 +459,79 @@ int mpenv_wire_error(mpenv_manager *mgr, uint32_t *out);
  * reached the read (record an event after it).  Clears REFUSED like
  * mpenv_wire_error. */
 int mpenv_wire_error_async(mpenv_manager *mgr, uint32_t *out, void *hip_stream);
+
+/* Extension, world checkpoints (no reference counterpart; its curriculum
+ * snapshots hold positions only, mpenv_curriculum_snapshot): save the whole
+ * batch's state into a caller-owned device buffer, later restore every world,
+ * rewind some, or fork chosen worlds from chosen snapshot worlds.
+ *
+ * The snapshot is a byte blob of mpenv_state_bytes bytes without pointers: a
+ * 256-B header (magic, version, W, N, T, spawn track length, sim_flags, task,
+ * total bytes, section count), then one section per state buffer in
+ * declaration order, each at a multiple of 256 B, holding that buffer's rows
+ * for all worlds in world order with the live buffer's row layout
+ * (mpenv_state_section).  Inside: every internal state column, the damage
+ * and reset-key tables, the exported observation / lidar / last-known rows
+ * (so every export is right directly after a load, before any step), the
+ * input columns (actions, reset, world curriculum, policy, reward
+ * coefficients) and the visibility occluder hints.  Outside: the agent maps
+ * (constant zeros), SIM_CONTROL (one row shared by all worlds), the debug
+ * exports (gathered on request), statistics, wire and log buffers.
+ *
+ * save / load are asynchronous on hip_stream (null: the manager's own
+ * stream) and never synchronise; the caller orders them against
+ * mpenv_step_async by using one stream, as with mpenv_wire_pack, and orders
+ * the loads of one manager among themselves the same way.  Buffers must be
+ * 16-B aligned device memory outside the manager's own allocations.
+ *
+ * load: world_map_device NULL restores every world from its own snapshot
+ * world; otherwise it is int32[W] in device memory: map[d] = s (0 <= s < W)
+ * overwrites live world d with snapshot world s, -1 leaves world d as it is.
+ * The header and the map are checked on the device, in stream order: a
+ * header that is not this manager's (magic, version, W, N, T, track length,
+ * flags, task, bytes) raises MPENV_STATE_ERR_HEADER, a map entry outside
+ * [-1, W) MPENV_STATE_ERR_MAP; such a load still returns MPENV_OK and writes
+ * nothing at all.  mpenv_state_error returns the bits raised since its last
+ * call and clears them; it synchronises the device (not for the hot path).
+ *
+ * Semantics: a restored world continues bit for bit as the snapshot's world
+ * did, given the same actions.  A forked world (d <- s, d != s) does the same
+ * until its next episode reset, where it draws world d's own keys (the world
+ * id enters the RNG only there): forks decorrelate at episode boundaries.
+ * The captured step graph is untouched (it holds pointers and sizes only).
+ * mpenv_gpu_stream_step callers see restored outputs at their next step.  A
+ * LearnerWire sender's shadow does not learn of a load: its last-known
+ * history is stale until the next keyframe.  A snapshot is valid only for a
+ * manager with the same num_worlds, team size, scene, flags and task; it is
+ * not a file format across versions.
+ *
+ * MPENV_ERR_INVALID (mpenv_last_error names the reason): null arguments, a
+ * buffer that is not 16-B aligned or lies inside the manager's allocations,
+ * and any manager opened with replay_log_path, record_log_path or
+ * event_log_path (append-only files a rewind would desynchronise). */
+#define MPENV_STATE_ERR_HEADER 1u
+#define MPENV_STATE_ERR_MAP 2u
+int mpenv_state_bytes(mpenv_manager *mgr, int64_t *bytes);
+int mpenv_state_save(mpenv_manager *mgr, void *dst_device, void *hip_stream);
+int mpenv_state_load(mpenv_manager *mgr, const void *src_device, const int32_t *world_map_device,
+                     void *hip_stream);
+int mpenv_state_error(mpenv_manager *mgr, uint32_t *bits);
+/* The three sizes a snapshot's layout depends on, for mpenv_state_section. */
+int mpenv_state_dims(mpenv_manager *mgr, uint32_t *num_worlds, uint32_t *team_size, uint32_t *spawn_track_len);
+/* Section idx of the snapshot of a manager with these sizes; needs no manager
+ * and no GPU (like mpenv_export_layout).  name: the export's name without
+ * MPENV_EXPORT_ for an exported buffer (export_id its id), else the engine's
+ * name of the column (export_id -1); bytes = rows(row_kind) * row_bytes with
+ * row_kind 0 = per agent (W * 2 * team_size rows), 1 = per world, 2 = per
+ * (world, team).  Every output may be null.  idx -1 describes the whole blob:
+ * offset 0, bytes = mpenv_state_bytes, row_bytes = the number of sections,
+ * row_kind -1.  Any other idx outside [0, sections) is MPENV_ERR_INVALID. */
+int mpenv_state_section(int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len,
+                        const char **name, int64_t *offset, int64_t *bytes, int32_t *row_bytes,
+                        int32_t *row_kind, int32_t *export_id);
+/* MPENV_DTYPE_* of section idx's elements (its rows are row_bytes / element
+ * size of them; an exported section's dims are mpenv_export_layout's). */
+int mpenv_state_section_dtype(int32_t idx, int32_t *dtype);
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

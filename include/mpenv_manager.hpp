@@ -177,6 +177,28 @@ public:
     // extension: the Step graph enqueued on a caller stream without a sync
     void stepAsync(void *strm) { check(mpenv_step_async(mgr_, strm)); }
 
+    // extension: world checkpoints (mpenv.h mpenv_state_*).  snapshot / worldMap
+    // are device pointers; worldMap null restores every world, strm null is
+    // the manager's own stream.  loadState never synchronises: a refused
+    // snapshot or map shows in stateError() (MPENV_STATE_ERR_* bits).
+    int64_t stateBytes() const
+    {
+        int64_t b = 0;
+        check(mpenv_state_bytes(mgr_, &b));
+        return b;
+    }
+    void saveState(void *snapshot, void *strm = nullptr) { check(mpenv_state_save(mgr_, snapshot, strm)); }
+    void loadState(const void *snapshot, const int32_t *worldMap = nullptr, void *strm = nullptr)
+    {
+        check(mpenv_state_load(mgr_, snapshot, worldMap, strm));
+    }
+    uint32_t stateError()
+    {
+        uint32_t e = 0;
+        check(mpenv_state_error(mgr_, &e));
+        return e;
+    }
+
     Tensor resetTensor() const { return get(MPENV_EXPORT_RESET); }
     Tensor simControlTensor() const { return get(MPENV_EXPORT_SIM_CONTROL); }
     Tensor matchResultTensor() const { return get(MPENV_EXPORT_MATCH_RESULT); }

@@ -415,6 +415,72 @@ struct CopyBatch {
 };
 int launchCopyBatch(const CopyBatch &b, void *stream);
 
+// World checkpoints (state.hip; DESIGN.md §3 "World checkpoints").  A
+// snapshot is a position-independent byte blob: a 256-B StateHeader, then one
+// section per state buffer in declaration order, each at a multiple of 256 B,
+// holding that buffer's rows for all worlds in world order (world s's rows
+// are one contiguous span of every section).
+constexpr uint32_t kStateMagic = 0x3153504du; // "MPS1"
+constexpr uint32_t kStateVersion = 1;
+constexpr int kMaxStateSegs = 192;
+
+struct StateHeader {
+    uint32_t magic, version;
+    int32_t W, N, T, spawnTrackLen;
+    uint32_t simFlags;
+    int32_t task;
+    int64_t bytes;
+    int32_t sections, pad;
+    uint32_t reserved[52];
+};
+static_assert(sizeof(StateHeader) == 256, "state header");
+
+// One section as mpenv_state_section reports it (host only, no GPU).
+struct StateSectionInfo {
+    const char *name;  // the export's name without MPENV_EXPORT_, else the DevState member's
+    int64_t offset, bytes;
+    int32_t rowBytes, rowKind, exportId; // exportId -1: not an export
+    int32_t dtype;  // MPENV_DTYPE_* of the elements
+    int32_t member; // offsetof(DevState, <member>); dmgCol >= 0: column of dmg
+    int32_t dmgCol;
+};
+int stateNumSections();
+// false when idx is out of range
+bool stateSection(int idx, int64_t W, int64_t N, int64_t trackLen, StateSectionInfo &out);
+int64_t stateBytes(int64_t W, int64_t N, int64_t trackLen);
+
+// The device-resident descriptor table both checkpoint kernels run over,
+// built once at create (buildStateTab) and uploaded; segment 0 is the header
+// (its live copy is `hdr` below), so a save writes it with the same copy.
+struct StateSeg {
+    char *live;        // the live buffer (world 0's span)
+    int64_t off;       // section offset in the blob
+    int64_t bytes;     // W * span
+    int32_t span;      // bytes per world
+    int32_t gran;      // largest power of two <= 16 dividing span and the live address
+};
+struct StateTab {
+    StateHeader hdr;
+    StateSeg seg[kMaxStateSegs];
+    // streaming copy (save / full load): first block of each segment, then the total
+    int64_t first[kMaxStateSegs + 1];
+    // mapped load: the wide sections (a wave per world span; wideBlocks
+    // blocks each, in front) and the narrow ones (a lane per element; first
+    // block of each, counted from the end of the wide blocks)
+    int64_t firstNarrow[kMaxStateSegs + 1];
+    int32_t wideSeg[kMaxStateSegs], narrowSeg[kMaxStateSegs];
+    int64_t blocks, blocksMap, wideBlocks; // grids of the two kernels; blocks per wide section
+    int32_t nSeg, W, nWide, nNarrow;
+    uint32_t go;  // written by k_state_check, read by the load that follows it
+    uint32_t err; // MPENV_STATE_ERR_* (mpenv_state_error reads and clears)
+};
+// throws std::runtime_error for a section whose buffer is not allocated (a
+// table buffer that is neither a section nor exempt fails state.hip's build)
+void buildStateTab(const DevState &s, const SceneDev &sc, StateTab *dev, StateTab &host);
+int launchStateSave(const StateTab &host, StateTab *dev, char *dst, void *stream);
+// map == nullptr: every world from its own snapshot world
+int launchStateLoad(const StateTab &host, StateTab *dev, const char *src, const int32_t *map, void *stream);
+
 // Learner-exchange wire format (wire.hip)
 int64_t wireBytes(const DevState &s, bool keyframe);
 int launchWirePack(const DevState &s, char *dst, bool keyframe, uint32_t worldOffset, void *stream);

@@ -183,6 +183,11 @@ struct mpenv_manager {
     int32_t *wireEp = nullptr;   // [2][W] a shadow's episode counters of the last two messages
     int wireParity = 0;          // which half of wireEp holds the previous message's
     OutTab *outTabDev = nullptr; // gpuStreamStep's caller output buffers (engine.h OutTab)
+    // World checkpoints (state.hip): the descriptor table, its device copy,
+    // and which log mode (append-only files) rules them out for this manager
+    StateTab stateTab;
+    StateTab *stateTabDev = nullptr;
+    const char *stateRefused = nullptr;
 
     ~mpenv_manager()
     {
@@ -964,6 +969,13 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
             throw std::runtime_error("mpenv: num_worlds too large for one device (agent index division)");
         allocState(*m);
         openLogs(*m, cfg);
+        m->stateRefused = cfg->replay_log_path  ? "a manager opened with replay_log_path"
+                          : cfg->record_log_path ? "a manager opened with record_log_path"
+                          : cfg->event_log_path  ? "a manager opened with event_log_path"
+                                                 : nullptr;
+        m->stateTabDev = m->alloc<StateTab>(1);
+        buildStateTab(m->S, m->sc, m->stateTabDev, m->stateTab);
+        m->upload(m->stateTabDev, &m->stateTab, sizeof(StateTab));
         // the caller's path strings are not kept past create
         m->cfg.replay_log_path = m->cfg.record_log_path = m->cfg.event_log_path = nullptr;
         m->cfg.curriculum_data_path = nullptr;
@@ -1389,6 +1401,109 @@ int mpenv_wire_error(mpenv_manager *m, uint32_t *out)
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
     }
+    return MPENV_OK;
+}
+
+// World checkpoints (state.hip)
+static int stateUsable(mpenv_manager *m, const void *buf, const char *what)
+{
+    if (!m || !buf) return fail(MPENV_ERR_INVALID, "null argument");
+    if (m->stateRefused)
+        return fail(MPENV_ERR_INVALID, std::string("state checkpoints are not available for ") + m->stateRefused +
+                                           " (append-only log files would desynchronise)");
+    if ((uintptr_t)buf & 15u) return fail(MPENV_ERR_INVALID, std::string(what) + " must be 16-B aligned");
+    // a buffer inside one of the manager's allocations would alias live state
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)buf) == hipSuccess) {
+        if (std::find(m->allocations.begin(), m->allocations.end(), (void *)base) != m->allocations.end())
+            return fail(MPENV_ERR_INVALID, std::string(what) + " lies inside the manager's own allocations");
+    } else {
+        (void)hipGetLastError();
+    }
+    return MPENV_OK;
+}
+
+int mpenv_state_bytes(mpenv_manager *m, int64_t *bytes)
+{
+    if (!m || !bytes) return fail(MPENV_ERR_INVALID, "null argument");
+    *bytes = m->stateTab.hdr.bytes;
+    return MPENV_OK;
+}
+
+int mpenv_state_dims(mpenv_manager *m, uint32_t *num_worlds, uint32_t *team_size, uint32_t *spawn_track_len)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null argument");
+    if (num_worlds) *num_worlds = (uint32_t)m->S.W;
+    if (team_size) *team_size = (uint32_t)m->S.T;
+    if (spawn_track_len) *spawn_track_len = (uint32_t)m->sc.spawnTrackLen;
+    return MPENV_OK;
+}
+
+int mpenv_state_save(mpenv_manager *m, void *dst, void *stream)
+{
+    if (int rc = stateUsable(m, dst, "state snapshot buffer")) return rc;
+    if (launchStateSave(m->stateTab, m->stateTabDev, static_cast<char *>(dst), stream ? stream : (void *)m->stream))
+        return fail(MPENV_ERR_HIP, "state save launch failed");
+    return MPENV_OK;
+}
+
+int mpenv_state_load(mpenv_manager *m, const void *src, const int32_t *map, void *stream)
+{
+    if (int rc = stateUsable(m, src, "state snapshot buffer")) return rc;
+    if ((uintptr_t)map & 15u) return fail(MPENV_ERR_INVALID, "state world map must be 16-B aligned");
+    if (launchStateLoad(m->stateTab, m->stateTabDev, static_cast<const char *>(src), map,
+                        stream ? stream : (void *)m->stream))
+        return fail(MPENV_ERR_HIP, "state load launch failed");
+    return MPENV_OK;
+}
+
+int mpenv_state_error(mpenv_manager *m, uint32_t *bits)
+{
+    if (!m || !bits) return fail(MPENV_ERR_INVALID, "null argument");
+    try {
+        HIP_CHECK(hipDeviceSynchronize());
+        uint32_t v = 0;
+        HIP_CHECK(hipMemcpy(&v, &m->stateTabDev->err, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        *bits = v;
+        if (v) HIP_CHECK(hipMemset(&m->stateTabDev->err, 0, sizeof(uint32_t)));
+    } catch (const std::exception &e) {
+        return fail(MPENV_ERR_HIP, e.what());
+    }
+    return MPENV_OK;
+}
+
+int mpenv_state_section(int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len,
+                        const char **name, int64_t *offset, int64_t *bytes, int32_t *row_bytes, int32_t *row_kind,
+                        int32_t *export_id)
+{
+    if (num_worlds == 0 || team_size == 0 || team_size > (uint32_t)kMaxTeamSize)
+        return fail(MPENV_ERR_INVALID, "num_worlds must be >= 1 and team_size in [1, 6]");
+    if (spawn_track_len < (uint32_t)kMinSpawnTrack)
+        return fail(MPENV_ERR_INVALID, "spawn_track_len must be >= " + std::to_string(kMinSpawnTrack));
+    const int64_t W = num_worlds, N = 2 * (int64_t)team_size;
+    StateSectionInfo si;
+    if (idx == -1) {
+        si = { "blob", 0, stateBytes(W, N, spawn_track_len), stateNumSections(), -1, -1, MPENV_DTYPE_UINT8, 0, -1 };
+    } else if (!stateSection(idx, W, N, spawn_track_len, si)) {
+        return fail(MPENV_ERR_INVALID, "state section index " + std::to_string(idx) + " out of range");
+    }
+    if (name) *name = si.name;
+    if (offset) *offset = si.offset;
+    if (bytes) *bytes = si.bytes;
+    if (row_bytes) *row_bytes = si.rowBytes;
+    if (row_kind) *row_kind = si.rowKind;
+    if (export_id) *export_id = si.exportId;
+    return MPENV_OK;
+}
+
+int mpenv_state_section_dtype(int32_t idx, int32_t *dtype)
+{
+    StateSectionInfo si;
+    if (!dtype) return fail(MPENV_ERR_INVALID, "null argument");
+    if (!stateSection(idx, 1, 2, kMinSpawnTrack, si))
+        return fail(MPENV_ERR_INVALID, "state section index " + std::to_string(idx) + " out of range");
+    *dtype = si.dtype;
     return MPENV_OK;
 }
 

@@ -274,6 +274,30 @@ PYBIND11_MODULE(madrona_mp_env, m)
         .def("wire_error_async", [](PySimManager &s, uintptr_t out, uintptr_t stream) {
             check(mpenv_wire_error_async(s.h->mgr, reinterpret_cast<uint32_t *>(out), reinterpret_cast<void *>(stream)));
         }, py::arg("out"), py::arg("stream"))
+        // world checkpoints (include/mpenv.h mpenv_state_*): device pointers
+        // as integers, 0 = no world map / the manager's own stream
+        .def("state_bytes", [](PySimManager &s) {
+            int64_t b = 0;
+            check(mpenv_state_bytes(s.h->mgr, &b));
+            return b;
+        })
+        .def("state_dims", [](PySimManager &s) {
+            uint32_t w = 0, t = 0, l = 0;
+            check(mpenv_state_dims(s.h->mgr, &w, &t, &l));
+            return py::make_tuple(w, t, l);
+        })
+        .def("save_state", [](PySimManager &s, uintptr_t dst, uintptr_t stream) {
+            check(mpenv_state_save(s.h->mgr, reinterpret_cast<void *>(dst), reinterpret_cast<void *>(stream)));
+        }, py::arg("dst"), py::arg("stream") = 0)
+        .def("load_state", [](PySimManager &s, uintptr_t src, uintptr_t world_map, uintptr_t stream) {
+            check(mpenv_state_load(s.h->mgr, reinterpret_cast<const void *>(src),
+                                   reinterpret_cast<const int32_t *>(world_map), reinterpret_cast<void *>(stream)));
+        }, py::arg("src"), py::arg("world_map") = 0, py::arg("stream") = 0)
+        .def("state_error", [](PySimManager &s) {
+            uint32_t e = 0;
+            check(mpenv_state_error(s.h->mgr, &e));
+            return e;
+        })
         .def("set_world_groups", [](PySimManager &s, int32_t g) { check(mpenv_set_world_groups(s.h->mgr, g)); })
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
         .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
@@ -415,4 +439,29 @@ PYBIND11_MODULE(madrona_mp_env, m)
             d["sim"] = py::cast(s);
             return d;
         }, py::arg("xla_gpu") = true);
+
+    // mpenv_state_section (no manager, no GPU): (name, offset, bytes,
+    // row_bytes, row_kind, export_id, dtype, dims); dims are the export's for
+    // an exported section, else (rows, elements per row).  idx -1: the blob.
+    m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
+        const char *name = nullptr;
+        int64_t off = 0, bytes = 0;
+        int32_t rb = 0, kind = 0, eid = -1, dt = MPENV_DTYPE_UINT8;
+        check(mpenv_state_section(idx, num_worlds, team_size, spawn_track_len, &name, &off, &bytes, &rb, &kind, &eid));
+        std::vector<int64_t> dims;
+        if (idx >= 0) check(mpenv_state_section_dtype(idx, &dt));
+        if (eid >= 0) {
+            int32_t edt = 0, nd = 0;
+            int64_t d[8];
+            check(mpenv_export_layout(eid, num_worlds, team_size, &edt, &nd, d));
+            dims.assign(d, d + nd);
+        } else {
+            const int64_t es = dt == MPENV_DTYPE_UINT8 ? 1 : dt == MPENV_DTYPE_UINT16 ? 2 : dt == MPENV_DTYPE_UINT64 ? 8 : 4;
+            const int64_t rows = idx >= 0 ? bytes / rb : 1, per = idx >= 0 ? rb / es : bytes;
+            dims = { rows, per };
+        }
+        static const char *const kNames[] = { "int32", "float32", "uint32", "uint8", "uint16", "uint64" };
+        return py::make_tuple(std::string(name), off, bytes, rb, kind, eid, std::string(kNames[dt]),
+                              py::tuple(py::cast(dims)));
+    }, py::arg("idx"), py::arg("num_worlds"), py::arg("team_size"), py::arg("spawn_track_len") = 128);
 }
