@@ -533,6 +533,61 @@ int mpenv_state_section(int32_t idx, uint32_t num_worlds, uint32_t team_size, ui
  * size of them; an exported section's dims are mpenv_export_layout's). */
 int mpenv_state_section_dtype(int32_t idx, int32_t *dtype);
 
+/* In-sim policy inference (Manager::Config::policyWeightsPath, mgr.hpp:49;
+ * evalAgentPolicy, dnn.cpp:555-891, which the reference runs on the CPU only).
+ * While a checkpoint is loaded, every step -- mpenv_step, mpenv_step_async,
+ * mpenv_gpu_stream_step (after its input copy) -- first evaluates the frozen
+ * network for each agent whose AGENT_POLICY value is >= 0 on the engine's
+ * current observations and writes its PVP_DISCRETE_ACTION and
+ * PVP_DISCRETE_AIM_ACTION rows, drawing six keys from the agent's own RNG;
+ * agents with a negative policy id keep the actions they were given.  The
+ * network, its arithmetic and the sampling are DESIGN.md §2 definition 15:
+ * every value equals a CPU restatement bit for bit.  The captured step graph
+ * is not touched by a load or an unload.
+ *
+ * dir: the reference's converted-checkpoint directory, one file per tensor
+ * (i32 ndim, i32 shape[ndim], f32 data; kernels [in][out]; the file names
+ * loadPolicyWeights / loadNormParams open, dnn.cpp:1169-1437).
+ * mpenv_policy_check reads and validates it without a manager or a GPU:
+ * MPENV_ERR_IO for a file that cannot be opened or is short, MPENV_ERR_INVALID
+ * for a wrong rank or shape; mpenv_last_error names the file and the reason.
+ * mpenv_policy_load does the same, then uploads the parameters; it waits for
+ * the manager's stream.  MPENV_ERR_INVALID (reason named) for a manager opened
+ * with replay_log_path, record_log_path or event_log_path (the logged actions
+ * would not be the ones played), with MPENV_SIMFLAG_FULL_TEAM_POLICY, or
+ * directly after an mpenv_gpu_stream_step that wrote the observation rows
+ * into its caller's buffers only (load before the first such step or after a
+ * plain step); while a policy is loaded mpenv_gpu_stream_step keeps the
+ * engine's own rows current and copies every output.
+ * mpenv_policy_unload synchronises the device and frees the parameters; later
+ * steps are the steps of a manager that never loaded.
+ *
+ * mpenv_policy_forward: the network for every agent whatever its policy id,
+ * asynchronous on hip_stream (null: the manager's; use the stream the steps
+ * run on): logits_out_device [A][37] f32 (17 discrete: 3 moveAmount, 8
+ * moveAngle, 3 fire, 3 stand; then 13 yaw, 7 pitch); actions_out_device
+ * [A][6] i32 or null: the actions each agent's current RNG would sample.  It
+ * writes no engine state and does not advance the RNG.
+ *
+ * mpenv_debug_policy_dense (test hook): y[M][N] = x[M][K] . w[K][N] through
+ * the trunk's dense code (each output one k-ascending fmaf chain from +0);
+ * x, y in device memory, w_host in host memory, 1 <= K <= 512; synchronous.
+ *
+ * mpenv_debug_policy_step (measurement hook): the policy part of a step
+ * alone, asynchronous on hip_stream -- it writes the policy agents' actions
+ * and advances their RNG as a step would.  parts: bit 0 the selection, bit 1
+ * the embed kernel, bit 2 the trunk kernel (7 = all; the trunk alone reuses
+ * the selection and the embeddings of the last full call). */
+int mpenv_policy_check(const char *dir);
+int mpenv_policy_load(mpenv_manager *mgr, const char *dir);
+int mpenv_policy_unload(mpenv_manager *mgr);
+int mpenv_policy_loaded(mpenv_manager *mgr, int32_t *on);
+int mpenv_policy_forward(mpenv_manager *mgr, float *logits_out_device, int32_t *actions_out_device,
+                         void *hip_stream);
+int mpenv_debug_policy_step(mpenv_manager *mgr, int32_t parts, void *hip_stream);
+int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t M, int32_t K, const float *w_host,
+                             int32_t N, float *y_device, void *hip_stream);
+
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world
  * groups, stats or timing buffers; every other step replays it). */

@@ -162,6 +162,14 @@ public:
         c.world_id_offset = cfg.worldIDOffset;
         check(mpenv_create(&c, &mgr_));
         execMode_ = cfg.execMode;
+        // mgr.cpp loads policyWeightsPath into the sim's policyWeights; a
+        // checkpoint that does not load is an error, as the reference's asserts
+        if (cfg.policyWeightsPath != nullptr && mpenv_policy_load(mgr_, cfg.policyWeightsPath) != MPENV_OK) {
+            const std::string why = mpenv_last_error();
+            mpenv_destroy(mgr_);
+            mgr_ = nullptr;
+            throw std::runtime_error("mpenv: " + why);
+        }
     }
     ~Manager() { mpenv_destroy(mgr_); }
     Manager(const Manager &) = delete;
@@ -176,6 +184,23 @@ public:
     void gpuStreamStep(void *strm, void **buffers) { check(mpenv_gpu_stream_step(mgr_, strm, buffers)); }
     // extension: the Step graph enqueued on a caller stream without a sync
     void stepAsync(void *strm) { check(mpenv_step_async(mgr_, strm)); }
+
+    // extension: in-sim policy inference (mpenv.h mpenv_policy_*): while a
+    // checkpoint is loaded, step() first writes the actions of every agent
+    // whose AgentPolicy.idx >= 0 (evalAgentPolicy, dnn.cpp:555-891)
+    void loadPolicy(const char *dir) { check(mpenv_policy_load(mgr_, dir)); }
+    void unloadPolicy() { check(mpenv_policy_unload(mgr_)); }
+    bool policyLoaded() const
+    {
+        int32_t on = 0;
+        check(mpenv_policy_loaded(mgr_, &on));
+        return on != 0;
+    }
+    // logits [A][37] f32 and actions [A][6] i32 (or null) are device pointers
+    void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr)
+    {
+        check(mpenv_policy_forward(mgr_, logits, actions, strm));
+    }
 
     // extension: world checkpoints (mpenv.h mpenv_state_*).  snapshot / worldMap
     // are device pointers; worldMap null restores every world, strm null is

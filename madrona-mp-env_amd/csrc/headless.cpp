@@ -2,7 +2,11 @@
 // reference's src/headless.cpp:24-139): create a Manager, init, run steps,
 // print world-steps/s ("FPS") and agent-steps/s.
 //
-//   headless CUDA NUM_WORLDS NUM_STEPS SCENE_DIR [--rand-actions] [--team-size N]
+//   headless CUDA NUM_WORLDS NUM_STEPS SCENE_DIR [--rand-actions] [--team-size N] [--policy-weights DIR]
+//
+// --policy-weights loads a converted checkpoint (Config::policyWeightsPath)
+// and binds every agent to it: the frozen network picks the actions inside
+// the step.
 //
 // --rand-actions draws actions from the hash tape (mpenv_core.h tapeActions)
 // into a device buffer and copies them in before every step, as the
@@ -23,7 +27,8 @@ using namespace madronaMPEnv;
 int main(int argc, char *argv[])
 {
     if (argc < 5) {
-        fprintf(stderr, "%s TYPE NUM_WORLDS NUM_STEPS SCENE_DIR [--rand-actions] [--team-size N]\n", argv[0]);
+        fprintf(stderr, "%s TYPE NUM_WORLDS NUM_STEPS SCENE_DIR [--rand-actions] [--team-size N] [--policy-weights DIR]\n",
+                argv[0]);
         return 1;
     }
     const std::string type = argv[1];
@@ -36,9 +41,11 @@ int main(int argc, char *argv[])
     const std::string scene = argv[4];
     bool rand_actions = false;
     uint32_t team_size = 6;
+    const char *weights = nullptr;
     for (int i = 5; i < argc; i++) {
         if (!strcmp(argv[i], "--rand-actions")) rand_actions = true;
         else if (!strcmp(argv[i], "--team-size") && i + 1 < argc) team_size = (uint32_t)std::stoul(argv[++i]);
+        else if (!strcmp(argv[i], "--policy-weights") && i + 1 < argc) weights = argv[++i];
     }
     const std::string col = scene + "/collisions.bin", nav = scene + "/navmesh.bin",
                       spw = scene + "/spawns.bin", zon = scene + "/zones.bin";
@@ -55,8 +62,10 @@ int main(int argc, char *argv[])
         cfg.numPBTPolicies = 0;
         cfg.policyHistorySize = 1;
         cfg.map = { scene.c_str(), col.c_str(), nav.c_str(), spw.c_str(), zon.c_str(), Vector3::zero(), 0.f };
+        cfg.policyWeightsPath = weights;
         Manager mgr(cfg);
         mgr.init();
+        if (weights) mgr.setUniformAgentPolicy(AgentPolicy { 0 });
 
         const int64_t A = (int64_t)num_worlds * 2 * team_size;
         const int ring = 16;

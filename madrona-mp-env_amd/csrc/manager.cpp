@@ -25,6 +25,7 @@
 
 #include "engine.h"
 #include "mpenv.h"
+#include "policy.h"
 #include "scene.h"
 
 using namespace mpenv;
@@ -188,6 +189,23 @@ struct mpenv_manager {
     StateTab stateTab;
     StateTab *stateTabDev = nullptr;
     const char *stateRefused = nullptr;
+    // In-sim policy inference (policy.hip; DESIGN.md §2 definition 15): the
+    // parameter blob and work buffers live from load to unload; while
+    // polLoaded, every step first writes the policy agents' actions
+    PolicyDev polDev {};
+    bool polLoaded = false;
+    // the last step was a gpuStreamStep that wrote the observation rows into
+    // its caller's buffers only (OutTab): the engine's own rows, which the
+    // policy reads, are a step behind until a step writes them again
+    bool exportsStale = false;
+
+    void freePolicy()
+    {
+        polLoaded = false;
+        for (void *p : { (void *)polDev.blob, (void *)polDev.emb, (void *)polDev.list, (void *)polDev.count })
+            if (p) (void)hipFree(p);
+        polDev = PolicyDev {};
+    }
 
     ~mpenv_manager()
     {
@@ -219,6 +237,7 @@ struct mpenv_manager {
         for (FILE *f : { replayFile, recordFile, eventsFile, stepsFile })
             if (f) std::fclose(f);
         for (void *p : allocations) (void)hipFree(p);
+        freePolicy();
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -323,6 +342,9 @@ struct mpenv_manager {
 
     void runStep(hipStream_t st)
     {
+        // evalAgentPolicy runs ahead of the game systems (sim.cpp:5361-5365);
+        // in front of the captured graph, which a load or unload leaves alone
+        if (polLoaded && launchPolicyStep(S, polDev, st)) throw std::runtime_error("policy launch failed");
         preStep(st);
         launchStep(st);
         postStep(st);
@@ -1033,6 +1055,7 @@ int mpenv_step_async(mpenv_manager *m, void *stream)
     if (!m) return fail(MPENV_ERR_INVALID, "null manager");
     try {
         m->runStep(stream ? (hipStream_t)stream : m->stream);
+        m->exportsStale = false;
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
     }
@@ -1044,6 +1067,7 @@ int mpenv_step(mpenv_manager *m)
     if (!m) return fail(MPENV_ERR_INVALID, "null manager");
     try {
         m->runStep(m->stream);
+        m->exportsStale = false;
         HIP_CHECK(hipStreamSynchronize(m->stream));
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
@@ -1207,8 +1231,11 @@ int mpenv_gpu_stream_step(mpenv_manager *m, void *stream, void **buffers)
         // for every call); the rest -- the state-backed outputs (hp,
         // magazine, alive, last-known rows, rewards, dones, episode results)
         // -- is copied after the step.
+        // with a policy loaded the step writes the engine's own observation
+        // rows (the network's inputs at the next step) and every output is copied
         OutTab tab;
-        const bool direct = directTable(buffers, tab);
+        const bool direct = !m->polLoaded && directTable(buffers, tab);
+        m->exportsStale = direct;
         if (!direct) {
             // every output copied: the zero fills (1.6 GB of stores at C3)
             // beside the step, ordered after whatever the caller queued
@@ -1504,6 +1531,113 @@ int mpenv_state_section_dtype(int32_t idx, int32_t *dtype)
     if (!stateSection(idx, 1, 2, kMinSpawnTrack, si))
         return fail(MPENV_ERR_INVALID, "state section index " + std::to_string(idx) + " out of range");
     *dtype = si.dtype;
+    return MPENV_OK;
+}
+
+// In-sim policy inference (policy.cpp, policy.hip; DESIGN.md §2 definition 15)
+int mpenv_policy_check(const char *dir)
+{
+    std::string err;
+    const int rc = policyRead(dir, nullptr, err);
+    return rc == MPENV_OK ? MPENV_OK : fail(rc, err);
+}
+
+int mpenv_policy_load(mpenv_manager *m, const char *dir)
+{
+    if (!m || !dir) return fail(MPENV_ERR_INVALID, "null argument");
+    if (m->stateRefused)
+        return fail(MPENV_ERR_INVALID, std::string("in-sim policy inference is not available for ") + m->stateRefused +
+                                           " (the logged actions would not be the ones played)");
+    if (m->cfg.sim_flags & MPENV_SIMFLAG_FULL_TEAM_POLICY)
+        return fail(MPENV_ERR_INVALID, "in-sim policy inference is not available with SimFlags.FullTeamPolicy "
+                                       "(the full-team action columns and the policy would write the same actions)");
+    if (m->exportsStale)
+        return fail(MPENV_ERR_INVALID, "in-sim policy inference: the last mpenv_gpu_stream_step wrote the observations "
+                                       "into its caller's buffers only; load the policy before the first "
+                                       "mpenv_gpu_stream_step or after a plain step");
+    std::vector<float> blob;
+    std::string err;
+    if (const int rc = policyRead(dir, &blob, err)) return fail(rc, err);
+    try {
+        HIP_CHECK(hipSetDevice(m->gpu));
+        HIP_CHECK(hipStreamSynchronize(m->stream));
+        m->freePolicy();
+        auto dev = [&](size_t bytes) {
+            void *p = nullptr;
+            HIP_CHECK(hipMalloc(&p, bytes));
+            return p;
+        };
+        m->polDev.blob = static_cast<const float *>(dev(blob.size() * sizeof(float)));
+        m->polDev.emb = static_cast<float *>(dev((size_t)m->S.A * pol::kTrunkIn * sizeof(float)));
+        m->polDev.list = static_cast<int32_t *>(dev((size_t)m->S.A * sizeof(int32_t)));
+        m->polDev.count = static_cast<int32_t *>(dev(16));
+        m->upload((void *)m->polDev.blob, blob.data(), blob.size() * sizeof(float));
+        m->polLoaded = true;
+    } catch (const std::exception &e) {
+        m->freePolicy();
+        return fail(MPENV_ERR_HIP, e.what());
+    }
+    return MPENV_OK;
+}
+
+int mpenv_policy_unload(mpenv_manager *m)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null manager");
+    (void)hipSetDevice(m->gpu);
+    (void)hipDeviceSynchronize(); // a step on a caller's stream may still read the blob
+    m->freePolicy();
+    return MPENV_OK;
+}
+
+int mpenv_policy_loaded(mpenv_manager *m, int32_t *on)
+{
+    if (!m || !on) return fail(MPENV_ERR_INVALID, "null argument");
+    *on = m->polLoaded ? 1 : 0;
+    return MPENV_OK;
+}
+
+int mpenv_policy_forward(mpenv_manager *m, float *logits, int32_t *actions, void *stream)
+{
+    if (!m || !logits) return fail(MPENV_ERR_INVALID, "null argument");
+    if (!m->polLoaded) return fail(MPENV_ERR_INVALID, "no policy loaded (mpenv_policy_load)");
+    if (launchPolicyForward(m->S, m->polDev, logits, actions, stream ? stream : (void *)m->stream))
+        return fail(MPENV_ERR_HIP, "policy launch failed");
+    return MPENV_OK;
+}
+
+int mpenv_debug_policy_step(mpenv_manager *m, int32_t parts, void *stream)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null manager");
+    if (!m->polLoaded) return fail(MPENV_ERR_INVALID, "no policy loaded (mpenv_policy_load)");
+    if (parts < 1 || parts > kPolicyAll) return fail(MPENV_ERR_INVALID, "policy step: parts must be in [1, 7]");
+    if (launchPolicyStep(m->S, m->polDev, stream ? stream : (void *)m->stream, parts))
+        return fail(MPENV_ERR_HIP, "policy launch failed");
+    return MPENV_OK;
+}
+
+int mpenv_debug_policy_dense(mpenv_manager *m, const float *x, int32_t M, int32_t K, const float *w_host, int32_t N,
+                             float *y, void *stream)
+{
+    if (!m || !x || !w_host || !y) return fail(MPENV_ERR_INVALID, "null argument");
+    if (M < 1 || N < 1 || K < 1 || K > pol::kHidden)
+        return fail(MPENV_ERR_INVALID, "policy dense: M, N >= 1 and 1 <= K <= 512");
+    const int Np = (N + 63) / 64 * 64; // a wave takes two column tiles
+    std::vector<float> wide((size_t)K * Np, 0.f), packed((size_t)pol::packedFloats(K, Np));
+    for (int k = 0; k < K; k++) std::memcpy(&wide[(size_t)k * Np], &w_host[(size_t)k * N], sizeof(float) * (size_t)N);
+    pol::packB(wide.data(), K, Np, packed.data());
+    void *wp = nullptr;
+    try {
+        hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+        HIP_CHECK(hipMalloc(&wp, packed.size() * sizeof(float)));
+        HIP_CHECK(hipMemcpyAsync(wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        if (launchPolicyDense(x, M, K, static_cast<const float *>(wp), N, y, st))
+            throw std::runtime_error("policy dense launch failed");
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipFree(wp));
+    } catch (const std::exception &e) {
+        if (wp) (void)hipFree(wp);
+        return fail(MPENV_ERR_HIP, e.what());
+    }
     return MPENV_OK;
 }
 

@@ -1,0 +1,110 @@
+// policy.h — in-sim policy inference (DESIGN.md §2 definition 15): the fixed
+// architecture of the reference's evalAgentPolicy (src/dnn.cpp:555-891), the
+// layout of its parameters in one device blob, and the launchers.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+
+namespace mpenv {
+
+namespace pol {
+
+constexpr int kEmbed = 64;           // EMBED_SIZE (dnn.cpp:588)
+constexpr int kPosFreqs = 8;         // NUM_POSITION_EMBEDDING_FREQUENCIES (dnn.cpp:589)
+constexpr int kCoefs = 9;            // RewardHyperParams
+constexpr int kSelfIn = kSelfObs + kCoefs + 3 * kPosFreqs * 2; // 100 (dnn.cpp:594-597)
+constexpr int kFwdIn = kFwdRays * 4; // 256
+constexpr int kRearIn = kRearRays * 4; // 64
+constexpr int kTmSlots = 5, kOppSlots = 6;
+constexpr int kTrunkIn = 6 * kEmbed; // 384
+constexpr int kHidden = 512;         // MLP_BUFFER_SIZE (dnn.cpp:740)
+constexpr int kDiscreteLogits = 17;  // 3 + 8 + 3 + 3 (dnn.cpp:155-160)
+constexpr int kAimLogits = 20;       // 13 yaw + 7 pitch (consts.hpp discreteAimNum*Buckets)
+constexpr int kLogits = kDiscreteLogits + kAimLogits; // 37
+constexpr int kNumHeads = 6;         // moveAmount, moveAngle, fire, stand, yaw, pitch
+constexpr int kHeadPad = 64;         // the two heads as one 512 x 37 dense, columns padded to two MFMA tiles
+
+// Embed modules in blob order (the order evalAgentPolicy runs them).
+enum Module { kModSelf = 0, kModFwd, kModRear, kModTm, kModOpp, kModLk, kNumModules };
+constexpr int kModIn[kNumModules] = { kSelfIn, kFwdIn, kRearIn, kOtherObs, kOtherObs, kOtherObs };
+
+// Normalisation parameters: means, then inverse sigmas, each in this order.
+constexpr int kNormSelf = 0, kNormCoefs = kNormSelf + kSelfObs, kNormFwd = kNormCoefs + kCoefs,
+              kNormRear = kNormFwd + 4, kNormTm = kNormRear + 4, kNormOpp = kNormTm + kOtherObs,
+              kNormLk = kNormOpp + kOtherObs, kNormCount = kNormLk + kOtherObs; // 156
+
+// MFMA B-operand packing of a [K][N] kernel (v_mfma_f32_32x32x2_f32: lane l
+// holds B[k = l >> 5][j = l & 31]): column tile t (32 columns), k step s (two
+// rows), lane l -> W[2 s + (l >> 5)][32 t + (l & 31)] at ((t * K/2 + s) * 64 + l).
+// K is padded to even and N to a multiple of 32 with zeros (exact: a chain
+// that starts at +0 never holds -0, so adding +0 * x changes nothing).
+constexpr int64_t packedFloats(int K, int N) { return (int64_t)((N + 31) / 32) * ((K + 1) / 2) * 64; }
+
+// The blob, in floats.
+struct Layout {
+    int64_t normMean, normInv;
+    int64_t embedW[kNumModules];     // [K][64] as stored in the checkpoint ([in][out])
+    int64_t embedScale[kNumModules], embedBias[kNumModules];
+    int64_t trunkW[3];               // packed
+    int64_t trunkScale[3], trunkBias[3];
+    int64_t headW;                   // packed [512][37 -> 64]
+    int64_t headBias;                // 37 (padded to 64)
+    int64_t total;
+};
+
+inline Layout layout()
+{
+    Layout L {};
+    int64_t o = 0;
+    auto take = [&](int64_t n) { int64_t r = o; o += (n + 63) / 64 * 64; return r; }; // 256-B aligned pieces
+    L.normMean = take(kNormCount);
+    L.normInv = take(kNormCount);
+    for (int m = 0; m < kNumModules; m++) {
+        L.embedW[m] = take((int64_t)kModIn[m] * kEmbed);
+        L.embedScale[m] = take(kEmbed);
+        L.embedBias[m] = take(kEmbed);
+    }
+    for (int i = 0; i < 3; i++) {
+        L.trunkW[i] = take(packedFloats(i == 0 ? kTrunkIn : kHidden, kHidden));
+        L.trunkScale[i] = take(kHidden);
+        L.trunkBias[i] = take(kHidden);
+    }
+    L.headW = take(packedFloats(kHidden, kHeadPad));
+    L.headBias = take(kHeadPad);
+    L.total = o;
+    return L;
+}
+
+void packB(const float *w /*[K][N]*/, int K, int N, float *out /*packedFloats(K, N)*/);
+
+} // namespace pol
+
+// policy.cpp: reads and validates a converted-checkpoint directory
+// (loadPolicyWeights / loadNormParams, dnn.cpp:1066-1480); with `blob` also
+// builds the device blob.  Returns MPENV_OK, MPENV_ERR_IO (a file that cannot
+// be opened or is short) or MPENV_ERR_INVALID (rank / shape), `err` naming
+// the file and the reason.
+int policyRead(const char *dir, std::vector<float> *blob, std::string &err);
+
+// policy.hip
+struct PolicyDev {
+    const float *blob;   // pol::layout()
+    float *emb;          // [A][384] trunk inputs of the selected agents, by list position
+    int32_t *list;       // [A] selected agent ids
+    int32_t *count;      // device word: how many
+};
+// The step path: select policy >= 0, write their action columns, advance their RNG by 6.
+// parts: which of its kernels run (all in a step; mpenv_debug_policy_step times them apart --
+// the trunk alone reuses the list and the embeddings of the last full call).
+enum PolicyParts { kPolicySelect = 1, kPolicyEmbed = 2, kPolicyTrunk = 4, kPolicyAll = 7 };
+int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts = kPolicyAll);
+// Every agent, no engine state written: logits [A][37], actions [A][6] (or null).
+int launchPolicyForward(const DevState &s, const PolicyDev &p, float *logits, int32_t *actions, void *stream);
+// y[M][N] = x[M][K] . w through the trunk's MFMA dense; wPacked = pol::packB(w) in device memory.
+int launchPolicyDense(const float *x, int M, int K, const float *wPacked, int N, float *y, void *stream);
+
+} // namespace mpenv

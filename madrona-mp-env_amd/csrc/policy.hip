@@ -1,0 +1,542 @@
+// policy.hip — in-sim policy inference on gfx950 (DESIGN.md §2 definition 15,
+// §4 "Policy kernels"): the reference's evalAgentPolicy (src/dnn.cpp:555-891,
+// CPU only there) as three kernels on the step's stream.
+//
+//   k_pol_select  ids of the agents with policy >= 0, compacted (ballot +
+//                 prefix, one atomic per wave), so cost follows their number
+//   k_pol_embed   normalisation, position embedding and the 20 embeddings of
+//                 four agents per wave (lane = output feature, explicit fmaf
+//                 chains on the VALU); 384 floats per agent
+//   k_pol_trunk   64 agents per block, activations resident in LDS: the three
+//                 512-wide layers and both heads on v_mfma_f32_32x32x2_f32,
+//                 LayerNorm statistics one row per lane, Gumbel-max sampling
+//                 on the agent lanes
+//
+// Every dense output is one k-ascending fmaf chain from +0: the f32-input
+// MFMA computes exactly that (one rounding per product, k order), K is never
+// split across accumulators or waves, and zero padding of K is exact.
+#include <hip/hip_runtime.h>
+
+#include "policy.h"
+
+namespace mpenv {
+
+using namespace pol;
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kTileRows = 64;       // agents per trunk block
+constexpr int kLdx = 514;           // LDS row stride in floats: row r starts at bank 2 r, so the A-operand
+                                    // read (32 rows x 2 adjacent k) touches 64 different banks
+constexpr int kTrunkThreads = 512;  // 8 waves, 64 output columns each
+constexpr size_t kTrunkLds = (size_t)(kTileRows * kLdx + kHidden + 2 * kTileRows) * sizeof(float);
+constexpr size_t kDenseLds = (size_t)(kTileRows * kLdx) * sizeof(float);
+
+constexpr int kEmbedAgents = 4;     // agents per wave of k_pol_embed
+constexpr int kEmbedWaves = 4;
+constexpr int kEmbedRowsMax = kEmbedAgents * kOppSlots; // 24
+constexpr int kYStride = 65;
+
+__device__ __forceinline__ float negInf() { return mp::u2f(0xff800000u); }
+
+// acc[mt][nt] = X[row0 + 32 mt ..][0 .. 2 ksteps) . W[.., tile nt], X in LDS
+// (row stride kLdx), W packed (policy.h packB) with wp at the first tile.
+// Lane l feeds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; every
+// k step accumulates into the same registers, so each output is the chain
+// fma(a_k, b_k, ...) over k ascending.
+template <int MT, int NT>
+__device__ __forceinline__ void mfmaDense(const float *xs, int row0, int ksteps, const float *wp, f32x16 (&acc)[MT][NT])
+{
+    constexpr int U = 8; // k steps per chunk: the next chunk's operands are loaded while this one's MFMAs run
+    const int lane = threadIdx.x & 63;
+    const float *xa = xs + (row0 + (lane & 31)) * kLdx + (lane >> 5);
+    const float *wb = wp + lane;
+    const int64_t tileStride = (int64_t)ksteps * 64;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) acc[mt][nt][v] = 0.f;
+
+    float a[U][MT], b[U][NT], an[U][MT], bn[U][NT];
+    auto load = [&](float (&pa)[U][MT], float (&pb)[U][NT], int s0) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) pa[u][mt] = xa[mt * 32 * kLdx + 2 * (s0 + u)];
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) pb[u][nt] = wb[nt * tileStride + (int64_t)(s0 + u) * 64];
+        }
+    };
+    const int chunks = ksteps / U;
+    if (chunks > 0) load(a, b, 0);
+    for (int c = 0; c < chunks; c++) {
+        // the last chunk loads itself again (no branch in the loop; the values are not used)
+        load(an, bn, (c + 1 < chunks ? c + 1 : c) * U);
+        __builtin_amdgcn_sched_barrier(0); // keep the loads in front of the MFMAs (the scheduler sinks them to their uses)
+#pragma unroll
+        for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][mt], b[u][nt], acc[mt][nt], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) a[u][mt] = an[u][mt];
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) b[u][nt] = bn[u][nt];
+        }
+    }
+    for (int s = chunks * U; s < ksteps; s++) { // K / 2 not a multiple of the chunk (test shapes only)
+        float ta[MT], tb[NT];
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++) ta[mt] = xa[mt * 32 * kLdx + 2 * s];
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) tb[nt] = wb[nt * tileStride + (int64_t)s * 64];
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++)
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[mt], tb[nt], acc[mt][nt], 0, 0, 0);
+    }
+}
+
+// C/D map of the 32x32 MFMA: register v of lane l is row 8 (v >> 2) + 4 (l >> 5) + (v & 3), column l & 31.
+template <int MT, int NT>
+__device__ __forceinline__ void storeTiles(float *xs, int row0, int col0, const f32x16 (&acc)[MT][NT])
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const int r = row0 + 32 * mt + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3);
+                xs[r * kLdx + col0 + 32 * nt + (lane & 31)] = acc[mt][nt][v];
+            }
+}
+
+// sampleLogits (dnn.cpp:536-553): Gumbel-max; a strictly greater score wins,
+// bucket 0 if nothing beats -inf (u = 0 gives logf_(0) = -inf, so g = -inf).
+__device__ int32_t sampleHead(const float *lg, int nb, mp::RandKey k)
+{
+    int32_t best = 0;
+    float mx = negInf();
+    for (int i = 0; i < nb; i++) {
+        const float u = mp::keyUniform(mp::splitI(k, (uint32_t)i));
+        const float g = -mp::logf_(-mp::logf_(u));
+        const float score = lg[i] + g;
+        if (score > mx) {
+            mx = score;
+            best = i;
+        }
+    }
+    return best;
+}
+
+__global__ void __launch_bounds__(256) k_pol_select(DevState S, int32_t *list, int32_t *count)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool on = g < S.A && S.policy[g] >= 0;
+    const unsigned long long b = __ballot(on);
+    if (b == 0) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(count, (int)__popcll(b));
+    base = __shfl(base, 0);
+    if (on) list[base + (int)__popcll(b & ((1ull << lane) - 1ull))] = (int32_t)g;
+}
+
+// ---- k_pol_embed -----------------------------------------------------------
+
+// invStd * (x - mean) for `len` consecutive floats of one agent (the
+// normalize*Ob functions, dnn.cpp:193-379; parameters repeat every `period`)
+__device__ __forceinline__ void normSpan(const float *blob, const Layout &L, const float *src, int len, int param,
+                                         int period, float *dst, bool live)
+{
+    const int lane = threadIdx.x & 63;
+    for (int e = lane; e < len; e += 64) {
+        const int p = param + (e % period);
+        const float x = live ? src[e] : 0.f;
+        dst[e] = blob[L.normInv + p] * (x - blob[L.normMean + p]);
+    }
+}
+
+template <int R>
+__device__ __forceinline__ void embedDense(const float *W, const float *xin, int K, float (&acc)[R])
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+    // the next four weights are in flight while this group's chains advance
+    float w0 = W[0 * kEmbed + lane], w1 = W[1 * kEmbed + lane], w2 = W[2 * kEmbed + lane], w3 = W[3 * kEmbed + lane];
+    for (int k = 0; k < K; k += 4) {
+        const int kn = k + 4 < K ? k + 4 : k;
+        const float n0 = W[(kn + 0) * kEmbed + lane], n1 = W[(kn + 1) * kEmbed + lane];
+        const float n2 = W[(kn + 2) * kEmbed + lane], n3 = W[(kn + 3) * kEmbed + lane];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const float4 x = *reinterpret_cast<const float4 *>(xin + r * K + k);
+            acc[r] = mp::fma_(w0, x.x, acc[r]);
+            acc[r] = mp::fma_(w1, x.y, acc[r]);
+            acc[r] = mp::fma_(w2, x.z, acc[r]);
+            acc[r] = mp::fma_(w3, x.w, acc[r]);
+        }
+        w0 = n0;
+        w1 = n1;
+        w2 = n2;
+        w3 = n3;
+    }
+}
+
+// LayerNorm + leaky ReLU of R rows held one feature per lane
+// (evalFullyConnectedLayerWithLayerNormWithActivation, dnn.cpp:428-524): the
+// Welford pass over the 64 outputs in index order runs one row per lane.
+template <int R>
+__device__ __forceinline__ void embedNorm(float (&acc)[R], float *ybuf, float *stat, const float *scale,
+                                          const float *bias)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int r = 0; r < R; r++) ybuf[r * kYStride + lane] = acc[r];
+    __syncthreads();
+    if (lane < R) {
+        float mean = 0.f, m2 = 0.f;
+        for (int i0 = 0; i0 < kEmbed; i0 += 16) { // 16 values per LDS wait, not one
+            float y[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) y[j] = ybuf[lane * kYStride + i0 + j];
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const float delta = y[j] - mean;
+                mean = mp::fma_(delta, 1.f / (float)(i0 + j + 1), mean);
+                const float delta2 = y[j] - mean;
+                m2 = mp::fma_(delta, delta2, m2);
+            }
+        }
+        stat[2 * lane] = mean;
+        stat[2 * lane + 1] = mp::sqrt_(m2 / (float)kEmbed + 1e-6f);
+    }
+    __syncthreads();
+    const float sc = scale[lane], bs = bias[lane];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const float o = mp::fma_(sc / stat[2 * r + 1], acc[r] - stat[2 * r], bs);
+        acc[r] = o >= 0.f ? o : 1e-2f * o;
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(kEmbedWaves * 64) k_pol_embed(DevState S, PolicyDev P, Layout L, int useList)
+{
+    constexpr int G = kEmbedAgents;
+    __shared__ __attribute__((aligned(16))) float s_xin[kEmbedWaves][G * kFwdIn];
+    __shared__ float s_y[kEmbedWaves][kEmbedRowsMax * kYStride];
+    __shared__ float s_stat[kEmbedWaves][2 * kEmbedRowsMax];
+
+    const int64_t n = useList ? (int64_t)*P.count : S.A;
+    if ((int64_t)blockIdx.x * (kEmbedWaves * G) >= n) return; // the whole block (uniform)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float *xin = s_xin[wave], *ybuf = s_y[wave], *stat = s_stat[wave];
+    const float *blob = P.blob;
+
+    int64_t pos[G], agent[G];
+    bool live[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        pos[g] = ((int64_t)blockIdx.x * kEmbedWaves + wave) * G + g;
+        live[g] = pos[g] < n;
+        agent[g] = live[g] ? (useList ? (int64_t)P.list[pos[g]] : pos[g]) : 0;
+    }
+    auto emit = [&](int g, int mod, float v) {
+        if (live[g]) P.emb[pos[g] * kTrunkIn + mod * kEmbed + lane] = v;
+    };
+
+    { // self: observation, reward coefficients, position frequency embedding (dnn.cpp:593-624)
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            float *dst = xin + g * kSelfIn;
+            normSpan(blob, L, S.selfObs + agent[g] * kSelfObs, kSelfObs, kNormSelf, kSelfObs, dst, live[g]);
+            normSpan(blob, L, S.rewardCoefs + agent[g] * kCoefs, kCoefs, kNormCoefs, kCoefs, dst + kSelfObs, live[g]);
+            if (lane < 6 * kPosFreqs) { // positionFrequencyEmbedding (dnn.cpp:381-406): sin rows before cos rows
+                const int f = lane / 6, rem = lane % 6;
+                const float p = live[g] ? S.selfPos[agent[g] * 3 + rem % 3] : 0.f;
+                const float scaled = p * (float)(1 << f) * mp::kPi;
+                dst[kSelfObs + kCoefs + lane] = rem < 3 ? mp::sinf_(scaled) : mp::cosf_(scaled);
+            }
+        }
+        __syncthreads();
+        float acc[G];
+        embedDense<G>(blob + L.embedW[kModSelf], xin, kSelfIn, acc);
+        embedNorm<G>(acc, ybuf, stat, blob + L.embedScale[kModSelf], blob + L.embedBias[kModSelf]);
+#pragma unroll
+        for (int g = 0; g < G; g++) emit(g, kModSelf, acc[g]);
+    }
+    { // forward lidar (dnn.cpp:626-636)
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            normSpan(blob, L, S.fwdLidar + agent[g] * kFwdIn, kFwdIn, kNormFwd, 4, xin + g * kFwdIn, live[g]);
+        __syncthreads();
+        float acc[G];
+        embedDense<G>(blob + L.embedW[kModFwd], xin, kFwdIn, acc);
+        embedNorm<G>(acc, ybuf, stat, blob + L.embedScale[kModFwd], blob + L.embedBias[kModFwd]);
+#pragma unroll
+        for (int g = 0; g < G; g++) emit(g, kModFwd, acc[g]);
+    }
+    { // rear lidar (dnn.cpp:638-648)
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            normSpan(blob, L, S.rearLidar + agent[g] * kRearIn, kRearIn, kNormRear, 4, xin + g * kRearIn, live[g]);
+        __syncthreads();
+        float acc[G];
+        embedDense<G>(blob + L.embedW[kModRear], xin, kRearIn, acc);
+        embedNorm<G>(acc, ybuf, stat, blob + L.embedScale[kModRear], blob + L.embedBias[kModRear]);
+#pragma unroll
+        for (int g = 0; g < G; g++) emit(g, kModRear, acc[g]);
+    }
+    { // teammates: all 5 slots whatever the team size, max from -inf (dnn.cpp:650-672)
+        constexpr int R = G * kTmSlots;
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            normSpan(blob, L, S.tmObs + agent[g] * (kTmSlots * kOtherObs), kTmSlots * kOtherObs, kNormTm, kOtherObs,
+                     xin + g * kTmSlots * kOtherObs, live[g]);
+        __syncthreads();
+        float acc[R];
+        embedDense<R>(blob + L.embedW[kModTm], xin, kOtherObs, acc);
+        embedNorm<R>(acc, ybuf, stat, blob + L.embedScale[kModTm], blob + L.embedBias[kModTm]);
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            float cur = negInf();
+#pragma unroll
+            for (int s = 0; s < kTmSlots; s++) cur = mp::fmaxD(cur, acc[g * kTmSlots + s]);
+            emit(g, kModTm, cur);
+        }
+    }
+    { // opponents: the slot's embedding times its mask before the max (dnn.cpp:674-700)
+        constexpr int R = G * kOppSlots;
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            normSpan(blob, L, S.oppObs + agent[g] * (kOppSlots * kOtherObs), kOppSlots * kOtherObs, kNormOpp, kOtherObs,
+                     xin + g * kOppSlots * kOtherObs, live[g]);
+        __syncthreads();
+        float acc[R];
+        embedDense<R>(blob + L.embedW[kModOpp], xin, kOtherObs, acc);
+        embedNorm<R>(acc, ybuf, stat, blob + L.embedScale[kModOpp], blob + L.embedBias[kModOpp]);
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            float cur = negInf();
+#pragma unroll
+            for (int s = 0; s < kOppSlots; s++) {
+                const float mask = live[g] ? S.masks[agent[g] * kOppSlots + s] : 0.f;
+                cur = mp::fmaxD(cur, mask * acc[g * kOppSlots + s]);
+            }
+            emit(g, kModOpp, cur);
+        }
+    }
+    { // last-known opponents (dnn.cpp:702-726)
+        constexpr int R = G * kOppSlots;
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            normSpan(blob, L, S.lkObs + agent[g] * (kOppSlots * kOtherObs), kOppSlots * kOtherObs, kNormLk, kOtherObs,
+                     xin + g * kOppSlots * kOtherObs, live[g]);
+        __syncthreads();
+        float acc[R];
+        embedDense<R>(blob + L.embedW[kModLk], xin, kOtherObs, acc);
+        embedNorm<R>(acc, ybuf, stat, blob + L.embedScale[kModLk], blob + L.embedBias[kModLk]);
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            float cur = negInf();
+#pragma unroll
+            for (int s = 0; s < kOppSlots; s++) cur = mp::fmaxD(cur, acc[g * kOppSlots + s]);
+            emit(g, kModLk, cur);
+        }
+    }
+}
+
+// ---- k_pol_trunk -----------------------------------------------------------
+
+// useList: the step path (agents P.list[0 .. *P.count), actions into the
+// engine's columns, RNG advanced by 6).  Otherwise every agent, logits /
+// actions into the caller's buffers and no engine state written.
+__global__ void __launch_bounds__(kTrunkThreads) k_pol_trunk(DevState S, PolicyDev P, Layout L, int useList,
+                                                             float *logitsOut, int32_t *actionsOut)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *xs = lds;                          // [64][kLdx] activations
+    float *rcp = lds + kTileRows * kLdx;      // 1 / (i + 1)
+    float *stat = rcp + kHidden;              // mean, sigma per row
+
+    const int64_t n = useList ? (int64_t)*P.count : S.A;
+    const int64_t base = (int64_t)blockIdx.x * kTileRows;
+    if (base >= n) return;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const float *blob = P.blob;
+
+    rcp[tid] = 1.f / (float)(tid + 1);
+    for (int idx = tid; idx < kTileRows * kTrunkIn; idx += kTrunkThreads) {
+        const int r = idx / kTrunkIn, c = idx - r * kTrunkIn;
+        xs[r * kLdx + c] = base + r < n ? P.emb[(base + r) * kTrunkIn + c] : 0.f;
+    }
+    __syncthreads();
+
+    for (int layer = 0; layer < 3; layer++) {
+        const int ksteps = (layer == 0 ? kTrunkIn : kHidden) / 2;
+        f32x16 acc[2][2];
+        mfmaDense<2, 2>(xs, 0, ksteps, blob + L.trunkW[layer] + (int64_t)(2 * wave) * ksteps * 64, acc);
+        __syncthreads(); // every wave has read its inputs
+        storeTiles<2, 2>(xs, 0, 64 * wave, acc);
+        __syncthreads();
+        if (tid < kTileRows) { // Welford over the 512 outputs in index order (dnn.cpp:438-460)
+            const float *y = xs + tid * kLdx;
+            float mean = 0.f, m2 = 0.f;
+            for (int i0 = 0; i0 < kHidden; i0 += 16) { // 16 values and reciprocals per LDS wait, not one
+                float v[16], rc[16];
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    v[j] = y[i0 + j];
+                    rc[j] = rcp[i0 + j];
+                }
+#pragma unroll
+                for (int j = 0; j < 16; j++) {
+                    const float delta = v[j] - mean;
+                    mean = mp::fma_(delta, rc[j], mean);
+                    const float delta2 = v[j] - mean;
+                    m2 = mp::fma_(delta, delta2, m2);
+                }
+            }
+            stat[2 * tid] = mean;
+            stat[2 * tid + 1] = mp::sqrt_(m2 / (float)kHidden + 1e-6f);
+        }
+        __syncthreads();
+        { // column tid of every row (dnn.cpp:513-523, slope 0)
+            const float sc = blob[L.trunkScale[layer] + tid], bs = blob[L.trunkBias[layer] + tid];
+            for (int r = 0; r < kTileRows; r++) {
+                const float o = mp::fma_(sc / stat[2 * r + 1], xs[r * kLdx + tid] - stat[2 * r], bs);
+                xs[r * kLdx + tid] = o >= 0.f ? o : 0.f * o;
+            }
+        }
+        __syncthreads();
+    }
+
+    // both heads as one 512 x 64 dense: four waves, one 32 x 32 tile each
+    f32x16 hacc[1][1];
+    const int mt = wave & 1, nt = (wave >> 1) & 1;
+    if (wave < 4) mfmaDense<1, 1>(xs, 32 * mt, kHidden / 2, blob + L.headW + (int64_t)nt * (kHidden / 2) * 64, hacc);
+    __syncthreads();
+    if (wave < 4) storeTiles<1, 1>(xs, 32 * mt, 32 * nt, hacc);
+    __syncthreads();
+
+    if (tid >= kTileRows || base + tid >= n) return;
+    const int64_t g = useList ? (int64_t)P.list[base + tid] : base + tid;
+    float *lg = xs + tid * kLdx; // the agent's own row
+    for (int j = 0; j < kLogits; j++) lg[j] = lg[j] + blob[L.headBias + j];
+    if (logitsOut)
+        for (int j = 0; j < kLogits; j++) logitsOut[g * kLogits + j] = lg[j];
+    if (!useList && !actionsOut) return;
+
+    // moveAmount, moveAngle, fire, stand, yaw, pitch: one rngAdvance each (dnn.cpp:796-840)
+    constexpr int kBuckets[kNumHeads] = { 3, 8, 3, 3, 13, 7 };
+    mp::RNG rng;
+    rng.key.a = (uint32_t)S.rngA[g];
+    rng.key.b = (uint32_t)S.rngB[g];
+    rng.ctr = (uint32_t)S.rngCtr[g];
+    int32_t act[kNumHeads];
+    int at = 0;
+#pragma unroll
+    for (int h = 0; h < kNumHeads; h++) {
+        act[h] = sampleHead(lg + at, kBuckets[h], mp::rngAdvance(rng));
+        at += kBuckets[h];
+    }
+    if (useList) {
+        reinterpret_cast<int4 *>(S.discreteAction)[g] = make_int4(act[0], act[1], act[2], act[3]);
+        reinterpret_cast<int2 *>(S.discreteAim)[g] = make_int2(act[4], act[5]);
+        S.rngCtr[g] = (int32_t)rng.ctr;
+    } else {
+        for (int h = 0; h < kNumHeads; h++) actionsOut[g * kNumHeads + h] = act[h];
+    }
+}
+
+// mpenv_debug_policy_dense: one wave per 64 x 64 output tile through mfmaDense
+__global__ void __launch_bounds__(64) k_pol_dense(const float *x, int M, int K, const float *wp, int N, float *y)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
+    const int Kp = (K + 1) & ~1;
+    for (int idx = lane; idx < kTileRows * Kp; idx += 64) {
+        const int r = idx / Kp, c = idx - r * Kp;
+        lds[r * kLdx + c] = (row0 + r < M && c < K) ? x[(row0 + r) * K + c] : 0.f;
+    }
+    __syncthreads();
+    f32x16 acc[2][2];
+    mfmaDense<2, 2>(lds, 0, Kp / 2, wp + (int64_t)(2 * blockIdx.y) * (Kp / 2) * 64, acc);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const int64_t r = row0 + 32 * mt + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3);
+                const int c = 64 * blockIdx.y + 32 * nt + (lane & 31);
+                if (r < M && c < N) y[r * N + c] = acc[mt][nt][v];
+            }
+}
+
+int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
+
+int run(const DevState &s, const PolicyDev &p, int useList, float *logits, int32_t *actions, hipStream_t st,
+        int parts = kPolicyEmbed | kPolicyTrunk)
+{
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_pol_trunk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kTrunkLds) != hipSuccess)
+        return -1;
+    const Layout L = layout();
+    const int64_t perBlock = kEmbedWaves * kEmbedAgents;
+    if (parts & kPolicyEmbed)
+        hipLaunchKernelGGL(k_pol_embed, dim3((unsigned)((s.A + perBlock - 1) / perBlock)), dim3(kEmbedWaves * 64), 0,
+                           st, s, p, L, useList);
+    if (check(hipGetLastError())) return -1;
+    if (!(parts & kPolicyTrunk)) return 0;
+    hipLaunchKernelGGL(k_pol_trunk, dim3((unsigned)((s.A + kTileRows - 1) / kTileRows)), dim3(kTrunkThreads), kTrunkLds,
+                       st, s, p, L, useList, logits, actions);
+    return check(hipGetLastError());
+}
+
+} // namespace
+
+int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (parts & kPolicySelect) {
+        if (check(hipMemsetAsync(p.count, 0, sizeof(int32_t), st))) return -1;
+        hipLaunchKernelGGL(k_pol_select, dim3((unsigned)((s.A + 255) / 256)), dim3(256), 0, st, s, p.list, p.count);
+        if (check(hipGetLastError())) return -1;
+    }
+    return run(s, p, 1, nullptr, nullptr, st, parts);
+}
+
+int launchPolicyForward(const DevState &s, const PolicyDev &p, float *logits, int32_t *actions, void *stream)
+{
+    return run(s, p, 0, logits, actions, (hipStream_t)stream);
+}
+
+// wPacked: pol::packB of w with N padded to a multiple of 64 columns
+int launchPolicyDense(const float *x, int M, int K, const float *wPacked, int N, float *y, void *stream)
+{
+    if (M < 1 || N < 1 || K < 1 || K > kHidden) return -1;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_pol_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kDenseLds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(k_pol_dense, dim3((unsigned)((M + kTileRows - 1) / kTileRows), (unsigned)((N + 63) / 64)),
+                       dim3(64), kDenseLds, (hipStream_t)stream, x, M, K, wPacked, N, y);
+    return check(hipGetLastError());
+}
+
+} // namespace mpenv

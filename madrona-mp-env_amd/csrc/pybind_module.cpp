@@ -192,8 +192,9 @@ PYBIND11_MODULE(madrona_mp_env, m)
                          uint32_t sim_flags, Task task, uint32_t team_size, uint32_t num_pbt_policies,
                          uint32_t policy_history_size, const std::string &scene_path, bool train_flank,
                          py::object replay_log_path, py::object record_log_path, py::object event_log_path,
-                         py::object curriculum_data_path, uint32_t world_id_offset) {
-                 std::string replay, record, event, curric;
+                         py::object curriculum_data_path, uint32_t world_id_offset,
+                         py::object policy_weights_path) {
+                 std::string replay, record, event, curric, weights;
                  mpenv_config cfg = {};
                  cfg.exec_mode = (int32_t)exec_mode;
                  cfg.gpu_id = (int32_t)gpu_id;
@@ -220,6 +221,11 @@ PYBIND11_MODULE(madrona_mp_env, m)
                      py::gil_scoped_release nogil;
                      check(mpenv_create(&cfg, &h->mgr));
                  }
+                 // Manager::Config::policyWeightsPath (mgr.hpp:49): loaded after the create, failing loudly
+                 if (!policy_weights_path.is_none()) {
+                     weights = py::str(policy_weights_path);
+                     check(mpenv_policy_load(h->mgr, weights.c_str()));
+                 }
                  return PySimManager { h };
              }),
              py::arg("exec_mode"), py::arg("gpu_id"), py::arg("num_worlds"), py::arg("rand_seed"),
@@ -227,7 +233,8 @@ PYBIND11_MODULE(madrona_mp_env, m)
              py::arg("num_pbt_policies"), py::arg("policy_history_size"), py::arg("scene_path"),
              py::arg("train_flank") = false, py::arg("replay_log_path") = py::none(),
              py::arg("record_log_path") = py::none(), py::arg("event_log_path") = py::none(),
-             py::arg("curriculum_data_path") = py::none(), py::arg("world_id_offset") = 0)
+             py::arg("curriculum_data_path") = py::none(), py::arg("world_id_offset") = 0,
+             py::arg("policy_weights_path") = py::none())
         .def("init", [](PySimManager &s) { py::gil_scoped_release nogil; check(mpenv_init(s.h->mgr)); })
         .def("step", [](PySimManager &s) { py::gil_scoped_release nogil; check(mpenv_step(s.h->mgr)); })
         .def("step_async", [](PySimManager &s, uintptr_t stream) {
@@ -274,6 +281,21 @@ PYBIND11_MODULE(madrona_mp_env, m)
         .def("wire_error_async", [](PySimManager &s, uintptr_t out, uintptr_t stream) {
             check(mpenv_wire_error_async(s.h->mgr, reinterpret_cast<uint32_t *>(out), reinterpret_cast<void *>(stream)));
         }, py::arg("out"), py::arg("stream"))
+        // in-sim policy inference (include/mpenv.h mpenv_policy_*): logits
+        // [A][37] f32 and actions [A][6] i32 are device pointers as integers
+        .def("load_policy", [](PySimManager &s, const std::string &dir) {
+            check(mpenv_policy_load(s.h->mgr, dir.c_str()));
+        }, py::arg("dir"))
+        .def("unload_policy", [](PySimManager &s) { check(mpenv_policy_unload(s.h->mgr)); })
+        .def("policy_loaded", [](PySimManager &s) {
+            int32_t on = 0;
+            check(mpenv_policy_loaded(s.h->mgr, &on));
+            return on != 0;
+        })
+        .def("policy_forward", [](PySimManager &s, uintptr_t logits, uintptr_t actions, uintptr_t stream) {
+            check(mpenv_policy_forward(s.h->mgr, reinterpret_cast<float *>(logits), reinterpret_cast<int32_t *>(actions),
+                                       reinterpret_cast<void *>(stream)));
+        }, py::arg("logits"), py::arg("actions") = 0, py::arg("stream") = 0)
         // world checkpoints (include/mpenv.h mpenv_state_*): device pointers
         // as integers, 0 = no world map / the manager's own stream
         .def("state_bytes", [](PySimManager &s) {
@@ -443,6 +465,8 @@ PYBIND11_MODULE(madrona_mp_env, m)
     // mpenv_state_section (no manager, no GPU): (name, offset, bytes,
     // row_bytes, row_kind, export_id, dtype, dims); dims are the export's for
     // an exported section, else (rows, elements per row).  idx -1: the blob.
+    // mpenv_policy_check: validates a converted-checkpoint directory (no manager, no GPU)
+    m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;
         int64_t off = 0, bytes = 0;
