@@ -911,18 +911,70 @@ __device__ DmgOut applyDmgD(const DevState &S, int64_t g)
 // does not evaluate them one after another (k_sim, resetPreD).
 constexpr int kPreDraws = 10;
 
-// What the world lane's spawn loop reads about its world's agents, kept in
-// LDS by k_sim (null members: read memory): positions [N][3] and alive
-// bytes, both updated as agents spawn (the respawn scoring sees earlier
-// spawns), and each agent's flags before the spawn (as float bits).
-// tabA / tabB / tabC: LDS copies of the scene's spawn lists (aSpawns,
-// bSpawns, commonRespawns), or null.
-struct SpawnLds {
-    float *pos;
-    uint8_t *alive;
-    const float *flags;
+// The spawn and reset code below is compiled per caller from three choices,
+// each a small type: where "my world's agents" are read (MemAgents,
+// LdsAgents), where an agent's draw keys come from (DrawnKeys, PreparedKeys)
+// and what happens to a chosen spawn (SpawnApply, SpawnRecord).
+
+// The world's agents in memory (one lane per world: k_construct and
+// k_reset_only); tabA / tabB / tabC: the scene's aSpawns, bSpawns, commonRespawns.
+struct MemAgents {
+    const DevState &S;
+    int64_t g0;
     const Spawn *tabA, *tabB, *tabC;
+    __device__ Vec3 pos(int j) const { return ldPos(S, g0 + j); }
+    __device__ bool alive(int j) const { return S.alive[g0 + j] != 0.f; }
+    __device__ int32_t flags(int j) const { return S.flags[g0 + j]; }
+    __device__ void markSpawned(int, Vec3) const {} // (the spawn's own stores are what later reads see)
 };
+
+// The world's agents in k_sim's LDS: positions [N][3] and alive bytes, both
+// updated as agents spawn (the respawn scoring sees earlier spawns), each
+// agent's flags before the spawn (as float bits), and LDS copies of the
+// scene's spawn lists (aSpawns, bSpawns, commonRespawns).
+struct LdsAgents {
+    float *posL;
+    uint8_t *aliveL;
+    const float *flagsL;
+    const Spawn *tabA, *tabB, *tabC;
+    __device__ Vec3 pos(int j) const { return v3(posL[3 * j], posL[3 * j + 1], posL[3 * j + 2]); }
+    __device__ bool alive(int j) const { return aliveL[j] != 0; }
+    __device__ int32_t flags(int j) const { return __float_as_int(flagsL[j]); }
+    __device__ void markSpawned(int j, Vec3 p) const
+    {
+        posL[3 * j] = p.x; posL[3 * j + 1] = p.y; posL[3 * j + 2] = p.z;
+        aliveL[j] = 1;
+    }
+};
+
+// Every draw from the agent's RNG in memory.
+struct DrawnKeys {
+    static constexpr bool kPrepared = false;
+    __device__ RNG rng(const DevState &S, int64_t g, int) const { return ldRng(S, g); }
+    __device__ RandKey next(int, RNG &r) const { return rngAdvance(r); }
+};
+
+// A world reset whose agents' lanes ran resetPreD: pre holds, per agent, its
+// fresh RNG key, then the keys of its first kPreDraws draws (the same keys
+// splitI(rng.key, ctr) the RNG would produce).
+struct PreparedKeys {
+    static constexpr bool kPrepared = true;
+    const RandKey *pre;
+    __device__ const RandKey *draws(int ai) const { return pre + ai * (kPreDraws + 1) + 1; }
+    __device__ RNG rng(const DevState &, int64_t, int ai) const { return makeRNG(pre[ai * (kPreDraws + 1)]); }
+    __device__ RandKey next(int ai, RNG &r) const
+    {
+        const RandKey k = r.ctr < (uint32_t)kPreDraws ? draws(ai)[r.ctr] : splitI(r.key, r.ctr);
+        r.ctr += 1;
+        return k;
+    }
+};
+
+// A chosen spawn is applied at once by the world lane (spawnApplyD), or
+// recorded for the agent's own lane to apply (k_sim, LDS): rec is the
+// world's records, kSpawnRec floats per agent.
+struct SpawnApply { static constexpr bool kRecord = false; };
+struct SpawnRecord { static constexpr bool kRecord = true; float *rec; };
 
 // World values the spawn loop reads once (not per agent).
 struct SpawnWorld {
@@ -930,33 +982,118 @@ struct SpawnWorld {
     uint32_t curStep;
 };
 
+__device__ __forceinline__ SpawnWorld ldSpawnWorldD(const DevState &S, int w)
+{
+    return SpawnWorld{ S.teamA[w], S.curZone[w], S.episodeCurr[w], (uint32_t)S.curStep[w] };
+}
+
+// The world's dead agents as a bit mask (utils.cpp:767-780: fixed before the loop).
+template <class Agents>
+__device__ __forceinline__ uint32_t deadMaskD(const Agents &A, int N)
+{
+    uint32_t dead = 0;
+    #pragma unroll 1
+    for (int k = 0; k < N; k++)
+        if (!A.alive(k)) dead |= 1u << k;
+    return dead;
+}
+
 // Spawn indices taken so far in a world reset's loop, per team list (bits
-// 0..127).  The reset cleared both lists just before (resetPreD), so
+// 0..127).  The reset cleared both lists just before (clearSpawnTrackD), so
 // "tracker[idx] == curStep" holds exactly for the indices taken here.
 struct SpawnTaken {
     uint64_t a0, a1, b0, b1;
 };
 
+// A chosen spawn: what spawnApplyD needs besides the agent's flags.  rngCtr
+// >= 0: the agent's RNG counter after its spawn draws (its key is unchanged).
+struct Spawned {
+    Vec3 pt;
+    float yaw, hp;
+    int32_t mag, rngCtr;
+};
+
+// A Spawned as k_sim's world lane leaves it in LDS for the agent's lane:
+// position, yaw, hp, then magazine and RNG counter as float bits.
+constexpr int kSpawnRec = 8;
+
+__device__ __forceinline__ void stSpawnRecD(float *r, const Spawned &s)
+{
+    r[0] = s.pt.x; r[1] = s.pt.y; r[2] = s.pt.z; r[3] = s.yaw;
+    r[4] = s.hp; r[5] = __int_as_float(s.mag); r[6] = __int_as_float(s.rngCtr);
+}
+
+__device__ __forceinline__ Spawned ldSpawnRecD(const float *r)
+{
+    return Spawned{ v3(r[0], r[1], r[2]), r[3], r[4], __float_as_int(r[5]), __float_as_int(r[6]) };
+}
+
+// A point and yaw inside spawn region s from four draws (standardSpawnPoint's
+// spawnAgent lambda).
+__device__ __forceinline__ void spawnInRegionD(const Spawn &s, RandKey kx, RandKey ky, RandKey kz, RandKey kyaw,
+                                               Vec3 &pt, float &yaw)
+{
+    const float x_rnd = keyUniform(kx), y_rnd = keyUniform(ky), z_rnd = keyUniform(kz), yaw_rnd = keyUniform(kyaw);
+    const float x_min = s.region.pMin.x, x_diff = s.region.pMax.x - x_min;
+    const float y_min = s.region.pMin.y, y_diff = s.region.pMax.y - y_min;
+    const float z_min = s.region.pMin.z, z_diff = s.region.pMax.z - z_min;
+    pt = v3(x_min + x_rnd * x_diff, y_min + y_rnd * y_diff, z_min + z_rnd * z_diff);
+    yaw = s.yawMin + yaw_rnd * (s.yawMax - s.yawMin);
+}
+
+// spawnAgents' draws from the world RNG before its loop; returns use_middle.
+__device__ __forceinline__ bool spawnPrologueD(const SceneDev &sc, RNG &base)
+{
+    // episodes[sampleI32(0, numEpisodes = 0)]: an empty range, the value is
+    // 0 whatever the key -- only the counter advances
+    base.ctr += 1;
+    return (sc.simFlags & kFlagSpawnInMiddle) && rngUniform(base) < 0.5f;
+}
+
+// utils.cpp:819-837 LearnShooting: a standard spawn point replaced
+__device__ __forceinline__ void learnShootingD(const SceneDev &sc, const SpawnWorld &sw, RNG &base, Vec3 &spawn_pt)
+{
+    if (!((sc.simFlags & kFlagEnableCurriculum) && sw.episodeCurr == 0)) return;
+    const bool north = spawn_pt.y > 0.f;
+    const float x = -700.f + rngUniform(base) * 1400.f;
+    const float y = rngUniform(base) * 350.f;
+    spawn_pt = v3(x, north ? y : -y, 0.f);
+}
+
+// The spawned agent's weapon, hp and magazine draws from the world RNG.
+__device__ __forceinline__ void loadoutD(const SceneDev &sc, RNG &base, Spawned &sp)
+{
+    // sampleI32(0, numWeaponTypes = 1) is 0 whatever the key: advance only
+    static_assert(c::kNumWeaponTypes == 1, "weapon draw shortcut assumes one weapon type");
+    base.ctr += 1;
+    sp.hp = 100.f;
+    sp.mag = c::kMagSize;
+    if (sc.simFlags & kFlagRandomizeHP) {
+        int tenth = rngI32(base, 1, 11);
+        sp.hp = float(tenth * 10);
+        sp.mag = rngI32(base, 0, c::kMagSize);
+    }
+}
+
 // One common respawn point's score for agent ai (utils.cpp:410-475 inside
 // standardSpawnPoint's respawn branch): recently used points, points near
 // any live agent, near live opponents, and near the zone score higher.
-__device__ __forceinline__ float respawnScoreD(const DevState &S, const Spawn *options, int s, int ai, int team,
-                                               uint32_t last_used, uint32_t cur_step, Vec3 zone_center,
-                                               const SpawnLds &L, int64_t g0)
+template <class Agents>
+__device__ __forceinline__ float respawnScoreD(const DevState &S, const Agents &A, int s, int ai, int team,
+                                               uint32_t last_used, uint32_t cur_step, Vec3 zone_center)
 {
     const int N = S.N;
     float score = 0.f;
     uint32_t elapsed = (uint32_t)(c::kDeltaT * float(cur_step - last_used));
     const float elapsed_weight = 0.1f, dist_weight = 0.01f;
     if (elapsed < 3.f) score += elapsed_weight * (3.f - elapsed);
-    Spawn sp = options[s];
+    Spawn sp = A.tabC[s];
     Vec3 spawn_pt = 0.5f * (sp.region.pMin + sp.region.pMax);
     #pragma unroll 1
     for (int j = 0; j < N; j++) {
         if (j == ai) continue;
-        if (L.alive ? L.alive[j] == 0 : S.alive[g0 + j] == 0.f) continue;
-        const Vec3 pj = L.pos ? v3(L.pos[3 * j], L.pos[3 * j + 1], L.pos[3 * j + 2]) : ldPos(S, g0 + j);
-        float dist = distance(spawn_pt, pj);
+        if (!A.alive(j)) continue;
+        float dist = distance(spawn_pt, A.pos(j));
         if (dist < 4.f * c::kAgentRadius) {
             score += 100000.f;
         } else {
@@ -969,48 +1106,32 @@ __device__ __forceinline__ float respawnScoreD(const DevState &S, const Spawn *o
     return score;
 }
 
-__device__ __forceinline__ void standardSpawnPointD(const DevState &S, const SceneDev &sc, int w, int ai, bool is_respawn,
-                                    bool use_middle, RNG &rng, Vec3 &out_pt, float &out_yaw,
-                                    const RandKey *pre, const SpawnWorld &sw, const SpawnLds &L, SpawnTaken &tk)
+template <bool kRespawn, class Agents, class Keys>
+__device__ __forceinline__ void standardSpawnPointD(const DevState &S, const SceneDev &sc, int w, int ai, bool use_middle,
+                                                    RNG &rng, Vec3 &out_pt, float &out_yaw, const Agents &A,
+                                                    const Keys &keys, const SpawnWorld &sw, SpawnTaken &tk)
 {
-    // rng's draws, from `pre` while the counter is inside it (same keys
-    // splitI(rng.key, ctr) the RNG would produce)
-    auto adv = [&]() {
-        const RandKey k = (pre && rng.ctr < (uint32_t)kPreDraws) ? pre[rng.ctr] : splitI(rng.key, rng.ctr);
-        rng.ctr += 1;
-        return k;
+    auto adv = [&]() { return keys.next(ai, rng); };
+    auto spawnAgent = [&](const Spawn &s) {
+        const RandKey kx = adv(), ky = adv(), kz = adv(), kyaw = adv();
+        spawnInRegionD(s, kx, ky, kz, kyaw, out_pt, out_yaw);
     };
-    const int N = S.N;
-    const int64_t g0 = (int64_t)w * N;
     const int team = ai / S.T;
     const uint32_t cur_step = sw.curStep;
     uint32_t *track = &S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen];
 
-    const Spawn *options;
-    auto spawnAgent = [&](int idx) {
-        Spawn s = options[idx];
-        float x_rnd = keyUniform(adv());
-        float y_rnd = keyUniform(adv());
-        float z_rnd = keyUniform(adv());
-        float yaw_rnd = keyUniform(adv());
-        float x_min = s.region.pMin.x, x_diff = s.region.pMax.x - x_min;
-        float y_min = s.region.pMin.y, y_diff = s.region.pMax.y - y_min;
-        float z_min = s.region.pMin.z, z_diff = s.region.pMax.z - z_min;
-        out_pt = v3(x_min + x_rnd * x_diff, y_min + y_rnd * y_diff, z_min + z_rnd * z_diff);
-        out_yaw = s.yawMin + yaw_rnd * (s.yawMax - s.yawMin);
-    };
-
-    if (!is_respawn || sc.numCommon == 0) {
+    if (!kRespawn || sc.numCommon == 0) {
+        const Spawn *options;
         uint32_t *tracker;
         int num_default, num_extra, num_spawns;
         const bool list_a = team == sw.teamA;
         if (list_a) {
-            options = L.tabA ? L.tabA : sc.aSpawns;
+            options = A.tabA;
             num_default = sc.numDefaultA;
             num_extra = sc.numA - sc.numDefaultA;
             tracker = track;
         } else {
-            options = L.tabB ? L.tabB : sc.bSpawns;
+            options = A.tabB;
             num_default = sc.numDefaultB;
             num_extra = sc.numB - sc.numDefaultB;
             tracker = track + sc.spawnTrackLen;
@@ -1021,40 +1142,36 @@ __device__ __forceinline__ void standardSpawnPointD(const DevState &S, const Sce
         } else {
             num_spawns = num_default;
         }
-        if (pre && !is_respawn && rng.ctr == 0 && num_spawns <= 128) {
-            // world reset: the agent's draw keys in one round of loads, the
-            // taken indices from tk instead of the tracker
-            RandKey k[kPreDraws];
-            #pragma unroll
-            for (int c = 0; c < kPreDraws; c++) k[c] = pre[c];
-            uint64_t &t0 = list_a ? tk.a0 : tk.b0, &t1 = list_a ? tk.a1 : tk.b1;
-            auto taken = [&](int idx) { return (((idx < 64 ? t0 : t1) >> (idx & 63)) & 1ull) != 0; };
-            int init_idx = keyI32(k[5], 0, num_spawns), used = 6;
-            #pragma unroll
-            for (int t = 4; t >= 0; t--) {
-                const int idx = keyI32(k[t], 0, num_spawns);
-                if (!taken(idx)) { init_idx = idx; used = t + 1; }
-            }
-            // draws used .. used + 3 position the agent (spawnAgent)
-            RandKey kk[4];
-            #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                kk[j] = k[6 + j];
+        if constexpr (Keys::kPrepared && !kRespawn) {
+            if (rng.ctr == 0 && num_spawns <= 128) {
+                // the agent's draw keys in one round of loads, the taken
+                // indices from tk instead of the tracker
+                RandKey k[kPreDraws];
                 #pragma unroll
-                for (int t = 5; t >= 1; t--)
-                    if (used == t) kk[j] = k[t + j];
+                for (int c = 0; c < kPreDraws; c++) k[c] = keys.draws(ai)[c];
+                uint64_t &t0 = list_a ? tk.a0 : tk.b0, &t1 = list_a ? tk.a1 : tk.b1;
+                auto taken = [&](int idx) { return (((idx < 64 ? t0 : t1) >> (idx & 63)) & 1ull) != 0; };
+                int init_idx = keyI32(k[5], 0, num_spawns), used = 6;
+                #pragma unroll
+                for (int t = 4; t >= 0; t--) {
+                    const int idx = keyI32(k[t], 0, num_spawns);
+                    if (!taken(idx)) { init_idx = idx; used = t + 1; }
+                }
+                // draws used .. used + 3 position the agent
+                RandKey kk[4];
+                #pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    kk[j] = k[6 + j];
+                    #pragma unroll
+                    for (int t = 5; t >= 1; t--)
+                        if (used == t) kk[j] = k[t + j];
+                }
+                rng.ctr = (uint32_t)(used + 4);
+                spawnInRegionD(options[init_idx], kk[0], kk[1], kk[2], kk[3], out_pt, out_yaw);
+                (init_idx < 64 ? t0 : t1) |= 1ull << (init_idx & 63);
+                tracker[init_idx] = cur_step;
+                return;
             }
-            rng.ctr = (uint32_t)(used + 4);
-            const Spawn sp = options[init_idx];
-            const float x_min = sp.region.pMin.x, x_diff = sp.region.pMax.x - x_min;
-            const float y_min = sp.region.pMin.y, y_diff = sp.region.pMax.y - y_min;
-            const float z_min = sp.region.pMin.z, z_diff = sp.region.pMax.z - z_min;
-            out_pt = v3(x_min + keyUniform(kk[0]) * x_diff, y_min + keyUniform(kk[1]) * y_diff,
-                        z_min + keyUniform(kk[2]) * z_diff);
-            out_yaw = sp.yawMin + keyUniform(kk[3]) * (sp.yawMax - sp.yawMin);
-            (init_idx < 64 ? t0 : t1) |= 1ull << (init_idx & 63);
-            tracker[init_idx] = cur_step;
-            return;
         }
         int init_idx = -1;
         for (int k = 0; k < 5; k++) {
@@ -1064,15 +1181,13 @@ __device__ __forceinline__ void standardSpawnPointD(const DevState &S, const Sce
             break;
         }
         if (init_idx == -1) init_idx = keyI32(adv(), 0, num_spawns);
-        spawnAgent(init_idx);
+        spawnAgent(options[init_idx]);
         tracker[init_idx] = cur_step;
         return;
     }
 
-    options = L.tabC ? L.tabC : sc.commonRespawns;
     uint32_t *rtrack = track + 2 * sc.spawnTrackLen;
-    const int cz = sw.cz;
-    AABB za = sc.tab->zoneAABB[cz];
+    AABB za = sc.tab->zoneAABB[sw.cz];
     Vec3 zone_center = 0.5f * (za.pMin + za.pMax);
     float best_score = kFltMax;
     int best_idx = -1;
@@ -1082,14 +1197,14 @@ __device__ __forceinline__ void standardSpawnPointD(const DevState &S, const Sce
         const uint32_t last_used = next_used;
         if (s + 1 < sc.numCommon) next_used = rtrack[s + 1];
         if (last_used == cur_step) continue;
-        const float score = respawnScoreD(S, options, s, ai, team, last_used, cur_step, zone_center, L, g0);
+        const float score = respawnScoreD(S, A, s, ai, team, last_used, cur_step, zone_center);
         if (score < best_score) {
             best_idx = s;
             best_score = score;
         }
     }
     if (best_idx < 0) best_idx = 0;
-    spawnAgent(best_idx);
+    spawnAgent(A.tabC[best_idx]);
     rtrack[best_idx] = cur_step;
 }
 
@@ -1118,27 +1233,28 @@ __device__ __forceinline__ ZoneBox zoneBoxD(const SceneDev &sc, int cz)
     return z;
 }
 
-// A spawned agent's own stores once its spawn point is chosen (the rest of
-// utils.cpp:734-948's loop body).  rng_ctr >= 0: the agent's RNG counter
-// after its spawn draws (its key is unchanged); flags: the agent's flags
-// before the spawn.  Run by the world lane, or (k_sim) by the agent's own
-// lane from the world lane's record.
+// A spawned agent's own stores once its spawn is chosen (the rest of
+// utils.cpp:734-948's loop body).  flags: the agent's flags before the
+// spawn.  Run by the world lane, or (k_sim) by the agent's own lane from the
+// world lane's record.  A reset (!is_respawn) also stores the agent's start
+// position (sx, sy, sz: resetPersistentEntities sets them from the spawn).
 __device__ __forceinline__ void spawnApplyD(const DevState &S, const SceneDev &sc, int64_t g, bool is_respawn,
-                                            Vec3 spawn_pt, float spawn_yaw, int32_t rng_ctr, float hp, int32_t mag,
-                                            int32_t flags, const ZoneBox &zb)
+                                            const Spawned &sp, int32_t flags, const ZoneBox &zb)
 {
+    Vec3 spawn_pt = sp.pt;
     stPos(S, g, spawn_pt);
     if (!is_respawn) { S.sx[g] = spawn_pt.x; S.sy[g] = spawn_pt.y; S.sz[g] = spawn_pt.z; }
-    if (rng_ctr >= 0) S.rngCtr[g] = rng_ctr;
-    stRot(S, g, qnormalize(angleAxis(spawn_yaw, kUp)));
-    stAim(S, g, computeAimD(spawn_yaw, 0.f));
+    if (sp.rngCtr >= 0) S.rngCtr[g] = sp.rngCtr;
+    stRot(S, g, qnormalize(angleAxis(sp.yaw, kUp)));
+    stAim(S, g, computeAimD(sp.yaw, 0.f));
     stVel(S, g, v3(0.f, 0.f, 0.f));
     S.weapon[g] = 0;
     // a respawn is followed by autoHealSystem (sim.cpp:1875-1890; alive, no
     // autoheal countdown)
+    float hp = sp.hp;
     if (is_respawn && hp < 100.f) hp = fminD(100.f, hp + c::kAutohealPerStep);
     S.hp[g] = hp;
-    S.magazine[2 * g] = mag;
+    S.magazine[2 * g] = sp.mag;
     S.magazine[2 * g + 1] = 0;
     S.respawnSteps[g] = is_respawn ? 0 : c::kRespawnInvincibleSteps;
     S.autohealSteps[g] = 0;
@@ -1169,142 +1285,78 @@ __device__ __forceinline__ void spawnApplyD(const DevState &S, const SceneDev &s
     S.alive[g] = 1.f;
 }
 
-// The world lane's spawn record of one agent for spawnApplyD on the agent's
-// lane (k_sim, LDS): position, yaw, hp, then magazine and RNG counter as
-// float bits.
-constexpr int kSpawnRec = 8;
-
-__device__ __forceinline__ void spawnApplyRecD(const DevState &S, const SceneDev &sc, int64_t g, bool is_respawn,
-                                               const float *rec, int32_t flags, const ZoneBox &zb)
+// utils.cpp:734-948 spawnAgents over the agents in dead_mask, drawing from
+// the world RNG base (the caller loads and stores it).
+template <bool kRespawn, class Agents, class Keys, class Sink>
+__device__ __forceinline__ void spawnAgentsD(const DevState &S, const SceneDev &sc, int w, const Agents &A,
+                                             const Keys &keys, const Sink &sink, uint32_t dead_mask,
+                                             const SpawnWorld &sw, RNG &base)
 {
-    spawnApplyD(S, sc, g, is_respawn, v3(rec[0], rec[1], rec[2]), rec[3], __float_as_int(rec[6]), rec[4],
-                __float_as_int(rec[5]), flags, zb);
-}
-
-// utils.cpp:734-948 spawnAgents
-// dead: the world's dead agents as a bit mask when the caller knows them
-// (k_sim: from applyDmgD's results in LDS; a reset: all), else -1 and read
-// from alive.  L: the caller's LDS copies of the world's agents (k_sim), or
-// null members.  A reset (!is_respawn) also stores each agent's start
-// position (sx, sy, sz: resetPersistentEntities sets them from the spawn).
-__device__ __forceinline__ void spawnAgentsD(const DevState &S, const SceneDev &sc, int w, bool is_respawn,
-                                             const RandKey *pre = nullptr, int64_t dead = -1,
-                                             SpawnLds L = SpawnLds{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr },
-                                             float *rec = nullptr, RNG *base_out = nullptr,
-                                             const SpawnWorld *sw_in = nullptr, const RNG *base_in = nullptr)
-{
+    if (dead_mask == 0) return;
     const int N = S.N;
     const int64_t g0 = (int64_t)w * N;
-    // Dead set fixed before the loop (utils.cpp:767-780).
-    uint32_t dead_mask = 0;
-    if (dead >= 0) {
-        dead_mask = (uint32_t)dead;
-    } else {
-        #pragma unroll 1
-        for (int i = 0; i < N; i++)
-            if (S.alive[g0 + i] == 0.f) dead_mask |= 1u << i;
-    }
-    if (dead_mask == 0) {
-        if (base_out) *base_out = base_in ? *base_in : ldWRng(S, w);
-        return;
-    }
-    // (a reset hands over the world values and RNG it has just stored)
-    RNG base = base_in ? *base_in : ldWRng(S, w);
-    SpawnWorld sw;
-    if (sw_in) {
-        sw = *sw_in;
-    } else {
-        sw.teamA = S.teamA[w];
-        sw.cz = S.curZone[w];
-        sw.curStep = (uint32_t)S.curStep[w];
-        sw.episodeCurr = S.episodeCurr[w];
-    }
-    // episodes[sampleI32(0, numEpisodes = 0)]: an empty range, the value is
-    // 0 whatever the key -- only the counter advances
-    base.ctr += 1;
-    bool use_middle = false;
-    if (sc.simFlags & kFlagSpawnInMiddle) use_middle = rngUniform(base) < 0.5f;
-    const bool randomize_hp = (sc.simFlags & kFlagRandomizeHP) != 0;
-    const int cz = sw.cz;
-    // the zone box in its own frame, once for every agent (record mode: the
-    // agents' lanes compute it)
+    const bool use_middle = spawnPrologueD(sc, base);
+    // the zone box in its own frame, once for every agent (recorded spawns:
+    // the agents' lanes compute it)
     ZoneBox zb;
-    if (!rec) zb = zoneBoxD(sc, cz);
+    if constexpr (!Sink::kRecord) zb = zoneBoxD(sc, sw.cz);
     SpawnTaken tk = { 0ull, 0ull, 0ull, 0ull };
 
     #pragma unroll 1
     for (int ai = 0; ai < N; ai++) {
         if (!(dead_mask & (1u << ai))) continue;
         const int64_t g = g0 + ai;
-        Vec3 spawn_pt;
-        float spawn_yaw;
-        int32_t rng_ctr = -1;
-        if ((sc.simFlags & kFlagHardcodedSpawns) && !is_respawn) {
+        Spawned sp;
+        sp.rngCtr = -1;
+        if ((sc.simFlags & kFlagHardcodedSpawns) && !kRespawn) {
             // utils.cpp:480-650 hardcodedSpawnPoint
             const int team = ai / S.T;
-            hardcodedSpawn((team == sw.teamA ? 0 : 3) + (ai - team * S.T), spawn_pt, spawn_yaw);
+            hardcodedSpawn((team == sw.teamA ? 0 : 3) + (ai - team * S.T), sp.pt, sp.yaw);
         } else if (sc.simFlags & kFlagNavmeshSpawn) {
             // utils.cpp:807-809
-            spawn_pt = navSamplePoint(sc.navTris, sc.navCdf, sc.numNavTris, rngAdvance(base));
-            spawn_yaw = rngUniform(base) * 2.f * kPi;
+            sp.pt = navSamplePoint(sc.navTris, sc.navCdf, sc.numNavTris, rngAdvance(base));
+            sp.yaw = rngUniform(base) * 2.f * kPi;
         } else {
-            const RandKey *apre = pre ? pre + ai * (kPreDraws + 1) : nullptr;
-            // a reset's agent RNG is the fresh key resetPreD stored (apre[0])
-            RNG rng = apre ? makeRNG(apre[0]) : ldRng(S, g);
-            standardSpawnPointD(S, sc, w, ai, is_respawn, use_middle, rng, spawn_pt, spawn_yaw,
-                                apre ? apre + 1 : nullptr, sw, L, tk);
-            rng_ctr = (int32_t)rng.ctr; // (the key is unchanged)
-            if ((sc.simFlags & kFlagEnableCurriculum) && sw.episodeCurr == 0) {
-                // utils.cpp:819-837 LearnShooting
-                const bool north = spawn_pt.y > 0.f;
-                const float x = -700.f + rngUniform(base) * 1400.f;
-                const float y = rngUniform(base) * 350.f;
-                spawn_pt = v3(x, north ? y : -y, 0.f);
-            }
+            RNG rng = keys.rng(S, g, ai);
+            standardSpawnPointD<kRespawn>(S, sc, w, ai, use_middle, rng, sp.pt, sp.yaw, A, keys, sw, tk);
+            sp.rngCtr = (int32_t)rng.ctr; // (the key is unchanged)
+            learnShootingD(sc, sw, base, sp.pt);
         }
-        if (L.pos) { L.pos[3 * ai] = spawn_pt.x; L.pos[3 * ai + 1] = spawn_pt.y; L.pos[3 * ai + 2] = spawn_pt.z; }
-        if (L.alive) L.alive[ai] = 1;
-        // sampleI32(0, numWeaponTypes = 1) is 0 whatever the key: advance only
-        static_assert(c::kNumWeaponTypes == 1, "weapon draw shortcut assumes one weapon type");
-        base.ctr += 1;
-        float hp = 100.f;
-        int32_t mag = c::kMagSize;
-        if (randomize_hp) {
-            int tenth = rngI32(base, 1, 11);
-            hp = float(tenth * 10);
-            mag = rngI32(base, 0, c::kMagSize);
-        }
-        if (rec) {
-            float *r = rec + ai * kSpawnRec;
-            r[0] = spawn_pt.x; r[1] = spawn_pt.y; r[2] = spawn_pt.z; r[3] = spawn_yaw;
-            r[4] = hp; r[5] = __int_as_float(mag); r[6] = __int_as_float(rng_ctr);
-        } else {
-            const int32_t flags = L.flags ? __float_as_int(L.flags[ai]) : S.flags[g];
-            spawnApplyD(S, sc, g, is_respawn, spawn_pt, spawn_yaw, rng_ctr, hp, mag, flags, zb);
-        }
+        // (every agent of a reset is dead: nothing scores against positions)
+        if constexpr (kRespawn) A.markSpawned(ai, sp.pt);
+        loadoutD(sc, base, sp);
+        if constexpr (Sink::kRecord) stSpawnRecD(sink.rec + ai * kSpawnRec, sp);
+        else spawnApplyD(S, sc, g, kRespawn, sp, A.flags(ai), zb);
     }
-    // (the caller that continues drawing takes the RNG back instead of
-    // reloading it behind every store above)
-    if (base_out) *base_out = base;
-    else stWRng(S, w, base);
+}
+
+// k_sim's respawn on the world lane: spawnAgents over the dead agents.
+template <class Sink>
+__device__ __forceinline__ void respawnSerialD(const DevState &S, const SceneDev &sc, int w, const LdsAgents &A,
+                                               const Sink &sink)
+{
+    const uint32_t dead = deadMaskD(A, S.N);
+    if (dead == 0) return;
+    RNG base = ldWRng(S, w);
+    spawnAgentsD<true>(S, sc, w, A, DrawnKeys{}, sink, dead, ldSpawnWorldD(S, w), base);
+    stWRng(S, w, base);
 }
 
 // k_sim's respawn (spawnAgents with is_respawn, common respawn points, no
 // navmesh spawns) with each dead agent's candidate scoring spread over its
 // world's N lanes: one dead agent per world per round, in agent order; every
-// lane scores candidates i, i + N, ... exactly as respawnScoreD (same
-// summation order), the world lane takes the lowest score (lowest index on
-// ties, as the sequential strict-< scan does), draws the spawn point and
-// writes the agent's record (spawnApplyRecD on the agent's lane applies it).
+// lane scores candidates i, i + N, ... with respawnScoreD, the world lane
+// takes the lowest score (lowest index on ties, as the sequential strict-<
+// scan does), draws the spawn point and writes the agent's record (the
+// agent's lane applies it).
 // Points taken earlier this step are tracked in LDS (usedL) next to the
 // tracker loads, so no lane reads back a tracker entry another lane stored.
 // Called by every thread of the block (block barriers).  coop: LDS scratch,
 // 4 floats per thread.
 __device__ __forceinline__ void respawnCoopD(const DevState &S, const SceneDev &sc, int w, int i, int wl, bool act,
-                                             const SpawnLds &L, float *rec, float *coop)
+                                             const LdsAgents &A, float *rec, float *coop)
 {
     const int N = S.N, T = S.T;
-    const int64_t g0 = (int64_t)w * N;
     const int B = (int)blockDim.x;
     float *const bestS = coop;          // per lane: best score
     float *const bestI = coop + B;      // per lane: its index (float bits)
@@ -1313,23 +1365,19 @@ __device__ __forceinline__ void respawnCoopD(const DevState &S, const SceneDev &
     const bool wl0 = act && i == 0;
     uint32_t rem = 0;
     RNG base;
-    int episode_curr = 0;
-    const bool randomize_hp = (sc.simFlags & kFlagRandomizeHP) != 0;
+    SpawnWorld sw;
     if (wl0) {
-        for (int k = 0; k < N; k++)
-            if (!L.alive[k]) rem |= 1u << k;
+        rem = deadMaskD(A, N);
         if (rem) {
             base = ldWRng(S, w);
-            episode_curr = S.episodeCurr[w];
-            base.ctr += 1; // episodes[sampleI32(0, 0)] (spawnAgentsD)
-            if (sc.simFlags & kFlagSpawnInMiddle) (void)rngUniform(base);
+            sw = ldSpawnWorldD(S, w);
+            (void)spawnPrologueD(sc, base);
         }
         usedL[2 * wl] = 0.f;
         usedL[2 * wl + 1] = 0.f;
     }
     const uint32_t *rtrack = act ? &S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen + 2 * sc.spawnTrackLen] : nullptr;
     uint32_t cur_step = 0u;
-    const Spawn *options = L.tabC;
     #pragma unroll 1
     for (;;) {
         int ai = -1;
@@ -1353,7 +1401,7 @@ __device__ __forceinline__ void respawnCoopD(const DevState &S, const SceneDev &
                 const bool taken = ((sp < 32 ? used0 : used1) >> (sp & 31)) & 1u;
                 const uint32_t last_used = taken ? cur_step : rtrack[sp];
                 if (last_used == cur_step) continue;
-                const float score = respawnScoreD(S, options, sp, a, team, last_used, cur_step, zone_center, L, g0);
+                const float score = respawnScoreD(S, A, sp, a, team, last_used, cur_step, zone_center);
                 if (score < bs) {
                     bs = score;
                     bi = sp;
@@ -1376,40 +1424,19 @@ __device__ __forceinline__ void respawnCoopD(const DevState &S, const SceneDev &
                 }
             }
             if (best_idx < 0) best_idx = 0;
-            const int64_t g = g0 + ai;
             // standardSpawnPoint's spawnAgent(best_idx), the agent's RNG
-            RNG rng = ldRng(S, g);
-            const Spawn sp = options[best_idx];
-            const float x_rnd = rngUniform(rng), y_rnd = rngUniform(rng), z_rnd = rngUniform(rng);
-            const float yaw_rnd = rngUniform(rng);
-            const float x_min = sp.region.pMin.x, x_diff = sp.region.pMax.x - x_min;
-            const float y_min = sp.region.pMin.y, y_diff = sp.region.pMax.y - y_min;
-            const float z_min = sp.region.pMin.z, z_diff = sp.region.pMax.z - z_min;
-            Vec3 spawn_pt = v3(x_min + x_rnd * x_diff, y_min + y_rnd * y_diff, z_min + z_rnd * z_diff);
-            const float spawn_yaw = sp.yawMin + yaw_rnd * (sp.yawMax - sp.yawMin);
+            RNG rng = ldRng(S, (int64_t)w * N + ai);
+            const RandKey kx = rngAdvance(rng), ky = rngAdvance(rng), kz = rngAdvance(rng), kyaw = rngAdvance(rng);
+            Spawned sp;
+            spawnInRegionD(A.tabC[best_idx], kx, ky, kz, kyaw, sp.pt, sp.yaw);
+            sp.rngCtr = (int32_t)rng.ctr;
             S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen + 2 * sc.spawnTrackLen + best_idx] = cur_step;
             if (best_idx < 32) usedL[2 * wl] = __int_as_float(__float_as_int(usedL[2 * wl]) | (int)(1u << best_idx));
             else usedL[2 * wl + 1] = __int_as_float(__float_as_int(usedL[2 * wl + 1]) | (int)(1u << (best_idx & 31)));
-            if ((sc.simFlags & kFlagEnableCurriculum) && episode_curr == 0) {
-                // utils.cpp:819-837 LearnShooting
-                const bool north = spawn_pt.y > 0.f;
-                const float x = -700.f + rngUniform(base) * 1400.f;
-                const float y = rngUniform(base) * 350.f;
-                spawn_pt = v3(x, north ? y : -y, 0.f);
-            }
-            L.pos[3 * ai] = spawn_pt.x; L.pos[3 * ai + 1] = spawn_pt.y; L.pos[3 * ai + 2] = spawn_pt.z;
-            L.alive[ai] = 1;
-            base.ctr += 1; // the weapon draw (spawnAgentsD)
-            float hp = 100.f;
-            int32_t mag = c::kMagSize;
-            if (randomize_hp) {
-                int tenth = rngI32(base, 1, 11);
-                hp = float(tenth * 10);
-                mag = rngI32(base, 0, c::kMagSize);
-            }
-            float *r = rec + ai * kSpawnRec;
-            r[0] = spawn_pt.x; r[1] = spawn_pt.y; r[2] = spawn_pt.z; r[3] = spawn_yaw;
-            r[4] = hp; r[5] = __int_as_float(mag); r[6] = __int_as_float((int32_t)rng.ctr);
+            learnShootingD(sc, sw, base, sp.pt);
+            A.markSpawned(ai, sp.pt);
+            loadoutD(sc, base, sp);
+            stSpawnRecD(rec + ai * kSpawnRec, sp);
             rem &= rem - 1u;
             if (rem == 0) stWRng(S, w, base);
         }
@@ -1431,6 +1458,7 @@ __device__ __forceinline__ int32_t resetAgentD(const DevState &S, int64_t g, Ran
     S.autohealSteps[g] = 0;
     S.wasShot[g] = 0;
     S.firedT[g] = -kFltMax;
+    // successfulKill/wasKilled/hasDied/reloadedFullMag = false
     const int32_t flags = S.flags[g] & (kFlagInZone | kFlagInSubZone);
     S.flags[g] = flags;
     S.alive[g] = 0.f;
@@ -1443,11 +1471,14 @@ __device__ __forceinline__ int32_t resetAgentD(const DevState &S, int64_t g, Ran
     return flags;
 }
 
-// pre != nullptr: every agent's resetAgentD already ran on its own lane and
-// pre holds, per agent, its RNG key then kPreDraws draw keys (resetPreD);
-// L (k_sim, LDS): the flags resetAgentD left and the spawn lists.
-// rec (k_sim, LDS, only without curriculum snapshots): spawn records for
-// the agents' lanes, which also do resetAgentTailD.
+// The reset of a world's spawn-usage tracker: entries first, first + stride, ...
+__device__ __forceinline__ void clearSpawnTrackD(const DevState &S, const SceneDev &sc, int w, int first, int stride)
+{
+    uint32_t *track = &S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen];
+    for (int k = first; k < 3 * sc.spawnTrackLen; k += stride) track[k] = 0xFFFFFFFFu;
+}
+
+// The reset agent's stores after its spawn.
 __device__ __forceinline__ void resetAgentTailD(const DevState &S, int64_t g)
 {
     for (int k = 0; k < 4; k++) S.discreteAction[4 * g + k] = 0;
@@ -1458,46 +1489,29 @@ __device__ __forceinline__ void resetAgentTailD(const DevState &S, int64_t g)
     rc[5] = 0.1f; rc[6] = 0.0005f; rc[7] = 1.f; rc[8] = 0.1f;
 }
 
+// PreparedKeys: every agent's resetAgentD and its share of the tracker clear
+// already ran on its own lane (resetPreD).  SpawnRecord (only without
+// curriculum snapshots, which rewrite agents after the spawn): the agents'
+// lanes apply the records and do resetAgentTailD.
+// sw, base: the world values and RNG initWorld has just stored.
+template <class Agents, class Keys, class Sink>
 __device__ __forceinline__ void resetPersistentEntitiesD(const DevState &S, const SceneDev &sc, int w, RandKey episode_key,
-                                         const RandKey *pre = nullptr,
-                                         SpawnLds L = SpawnLds{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr },
-                                         float *rec = nullptr, const SpawnWorld *sw_in = nullptr,
-                                         const RNG *base_in = nullptr)
+                                                         const Agents &A, const Keys &keys, const Sink &sink,
+                                                         const SpawnWorld &sw, RNG &base)
 {
     const int N = S.N;
     const int64_t g0 = (int64_t)w * N;
-    #pragma unroll 1
-    for (int i = 0; i < N && !pre; i++) {
-        const int64_t g = g0 + i;
-        stPos(S, g, v3(kFltMax, kFltMax, kFltMax));
-        RNG r = makeRNG(splitI(episode_key, (uint32_t)(i + 1)));
-        stRng(S, g, r);
-        S.landedOn[g] = -1;
-        S.respawnSteps[g] = 0;
-        S.autohealSteps[g] = 0;
-        S.wasShot[g] = 0;
-        S.firedT[g] = -kFltMax;
-        S.flags[g] = S.flags[g] & (kFlagInZone | kFlagInSubZone); // successfulKill/wasKilled/hasDied/reloadedFullMag = false
-        S.alive[g] = 0.f;
-        float4 *lk = reinterpret_cast<float4 *>(&S.lkObs[g * 6 * kOtherObs]);
-        for (int k = 0; k < 6 * kOtherObs / 4; k++) lk[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k < 18; k++) S.lkPos[g * 18 + k] = -1000.f;
-        S.bcPenalty[g] = 0.f;
-        S.bcLast[g] = -1;
-        S.bcSteps[g] = 0;
+    if constexpr (!Keys::kPrepared) {
+        #pragma unroll 1
+        for (int i = 0; i < N; i++) resetAgentD(S, g0 + i, splitI(episode_key, (uint32_t)(i + 1)));
+        clearSpawnTrackD(S, sc, w, 0, 1);
     }
-    if (!pre) {
-        uint32_t *track = &S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen];
-        for (int k = 0; k < 3 * sc.spawnTrackLen; k++) track[k] = 0xFFFFFFFFu;
-    }
-    // every agent is dead here (resetAgentD); spawnAgentsD also stores the
-    // start positions sx, sy, sz (= the spawn positions)
-    RNG base;
-    spawnAgentsD(S, sc, w, false, pre, pre ? (int64_t)((1u << N) - 1u) : -1, L, rec, &base, sw_in, base_in);
+    // every agent is dead here (resetAgentD)
+    spawnAgentsD<false>(S, sc, w, A, keys, sink, (1u << N) - 1u, sw, base);
 
     #pragma unroll 1
     for (int i = 0; i < N; i++) {
-        if (!rec) resetAgentTailD(S, g0 + i);
+        if constexpr (!Sink::kRecord) resetAgentTailD(S, g0 + i);
         // level_gen.cpp:427-446: nine discarded coefficient draws.
         base.ctr += 9;
     }
@@ -1544,10 +1558,9 @@ __device__ __forceinline__ void resetPersistentEntitiesD(const DevState &S, cons
 }
 
 // sim.cpp:732-833 initWorld
-__device__ __forceinline__ void initWorldD(const DevState &S, const SceneDev &sc, int w, bool triggered_reset, const int32_t *tc,
-                           const RandKey *pre = nullptr,
-                           SpawnLds L = SpawnLds{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr },
-                           float *rec = nullptr)
+template <class Agents, class Keys, class Sink>
+__device__ __forceinline__ void initWorldD(const DevState &S, const SceneDev &sc, int w, bool triggered_reset,
+                                           const int32_t *tc, const Agents &A, const Keys &keys, const Sink &sink)
 {
     const uint32_t world_id = sc.worldOffset + (uint32_t)w;
     S.matchValid[w] = 1; // matchID = worldID << 32 | curEpisodeIdx (sim.cpp:736-738)
@@ -1588,7 +1601,7 @@ __device__ __forceinline__ void initWorldD(const DevState &S, const SceneDev &sc
     S.stepsUntilPoint[w] = c::kZonePointInterval;
     S.subState[w] = 0; // every sub-zone: controlling -1, not contested / captured (sim.cpp:815-820)
     stWRng(S, w, base);
-    resetPersistentEntitiesD(S, sc, w, episode_key, pre, L, rec, &sw, &base);
+    resetPersistentEntitiesD(S, sc, w, episode_key, A, keys, sink, sw, base);
     S.filtAct0[w] = 0; S.filtAct1[w] = 0;
     S.filtMatched0[w] = 0; S.filtMatched1[w] = 0;
 }
@@ -1602,8 +1615,9 @@ __device__ __forceinline__ bool resetDueD(const DevState &S, const SceneDev &sc,
 // The per-agent half of a coming world reset, on the agent's own lane
 // (k_sim, before resetSystemD): the episode key initWorld will derive, the
 // agent's combat RNG key split_i(episodeKey, i + 1) and its first kPreDraws
-// draw keys into pre[0], pre[1..], the agent's resetPersistentEntities
-// stores, and its share of the spawn-usage tracker reset.
+// draw keys into pre[0], pre[1..] (PreparedKeys), the agent's
+// resetPersistentEntities stores, and its share of the spawn-usage tracker
+// reset.
 // Returns the agent's flags after its reset.
 __device__ __forceinline__ int32_t resetPreD(const DevState &S, const SceneDev &sc, int w, int i, RandKey *pre)
 {
@@ -1614,14 +1628,13 @@ __device__ __forceinline__ int32_t resetPreD(const DevState &S, const SceneDev &
     pre[0] = key;
     for (int c = 0; c < kPreDraws; c++) pre[1 + c] = splitI(key, (uint32_t)c);
     const int32_t flags = resetAgentD(S, (int64_t)w * S.N + i, key);
-    uint32_t *track = &S.spawnTrack[(int64_t)w * 3 * sc.spawnTrackLen];
-    for (int k = i; k < 3 * sc.spawnTrackLen; k += S.N) track[k] = 0xFFFFFFFFu;
+    clearSpawnTrackD(S, sc, w, i, S.N);
     return flags;
 }
 
-__device__ __forceinline__ void resetSystemD(const DevState &S, const SceneDev &sc, int w, const RandKey *pre = nullptr,
-                                             SpawnLds L = SpawnLds{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr },
-                                             float *rec = nullptr)
+template <class Agents, class Keys, class Sink>
+__device__ __forceinline__ void resetSystemD(const DevState &S, const SceneDev &sc, int w, const Agents &A,
+                                             const Keys &keys, const Sink &sink)
 {
     const int32_t force = S.reset[w];
     if (!resetDueD(S, sc, w)) return;
@@ -1639,72 +1652,14 @@ __device__ __forceinline__ void resetSystemD(const DevState &S, const SceneDev &
             S.worldCurr[w] = 1;
         }
     }
-    initWorldD(S, sc, w, force == 1, S.trainCtrl, pre, L, rec);
+    initWorldD(S, sc, w, force == 1, S.trainCtrl, A, keys, sink);
 }
 
 // ====================================================== per-world systems
-// sim.cpp:1892-1976 zoneSystem
-__device__ void zoneSystemD(const DevState &S, const SceneDev &sc, int w)
-{
-    const int N = S.N;
-    const int64_t g0 = (int64_t)w * N;
-    int cz = S.curZone[w];
-    int ctrl = S.controlling[w];
-    int zsr = S.zoneSteps[w];
-    int sup = S.stepsUntilPoint[w];
-    bool captured = S.captured[w] != 0;
-    if (ctrl != -1) zsr -= 1;
-    if (zsr == 0) {
-        cz += 1;
-        if (cz == sc.numZones) cz = 0;
-        captured = false;
-        zsr = c::kNumStepsPerZone;
-        sup = c::kZonePointInterval;
-        AABB za = sc.tab->zoneAABB[cz];
-        Vec3 center = (za.pMax + za.pMin) / 2.f;
-#pragma unroll 1
-        for (int i = 0; i < N; i++) S.minDistZone[g0 + i] = distance(ldPos(S, g0 + i), center);
-    }
-    AABB za = sc.tab->zoneAABB[cz];
-    Quat to_zone = qinv(angleAxis(sc.tab->zoneRot[cz], kUp));
-    za.pMin = rotateVec(to_zone, za.pMin);
-    za.pMax = rotateVec(to_zone, za.pMax);
-    int na = 0, nb = 0;
-#pragma unroll 1
-    for (int i = 0; i < N; i++) {
-        Vec3 p = ldPos(S, g0 + i);
-        p.z += c::kStandHeight / 2.f;
-        Vec3 pz = rotateVec(to_zone, p);
-        bool in = aabbContains(za, pz);
-        setFlag(S, g0 + i, kFlagInZone, in);
-        if (!in) continue;
-        if (i / S.T == 0) na += 1;
-        else nb += 1;
-    }
-    sup -= 1;
-    bool contested = na > 0 && nb > 0;
-    if (contested || (na == 0 && nb == 0)) {
-        ctrl = -1;
-        captured = false;
-        sup = c::kZonePointInterval;
-    } else if (na > 0 && nb == 0) {
-        if (ctrl != 0) { ctrl = 0; captured = false; sup = c::kZonePointInterval; }
-    } else if (na == 0 && nb > 0) {
-        if (ctrl != 1) { ctrl = 1; captured = false; sup = c::kZonePointInterval; }
-    }
-    S.curZone[w] = cz;
-    S.controlling[w] = ctrl;
-    S.zoneSteps[w] = zsr;
-    S.stepsUntilPoint[w] = sup;
-    S.captured[w] = captured ? 1 : 0;
-    S.contested[w] = contested ? 1 : 0;
-}
-
-// zoneSystem split for the step kernel: the world lane rotates the zone
-// (zonePreD), every agent lane tests itself against the zone box in
-// parallel (zoneInD; the world lane walked the N agents one load round trip
-// at a time), and the world lane counts the teams and stores (zonePostD).
-// Same arithmetic and stores as zoneSystemD, which the replay path keeps.
+// sim.cpp:1892-1976 zoneSystem, in three parts so that the step kernel can
+// run the middle one on every agent's lane: the world lane rotates the zone
+// (zonePreD), each agent is tested against the zone box (zoneInD), and the
+// world lane counts the teams and stores (zonePostD).
 struct ZonePre {
     int cz, ctrl, zsr, sup;
     bool captured;
@@ -1767,6 +1722,21 @@ __device__ __forceinline__ void zonePostD(const DevState &S, int w, ZonePre z, i
     S.stepsUntilPoint[w] = z.sup;
     S.captured[w] = z.captured ? 1 : 0;
     S.contested[w] = contested ? 1 : 0;
+}
+
+// zoneSystem on one lane (the replay path)
+__device__ void zoneSystemD(const DevState &S, const SceneDev &sc, int w)
+{
+    const int64_t g0 = (int64_t)w * S.N;
+    const ZonePre z = zonePreD(S, sc, w);
+    int na = 0, nb = 0;
+#pragma unroll 1
+    for (int i = 0; i < S.N; i++) {
+        if (!zoneInD(S, sc, z.cz, g0 + i)) continue;
+        if (i / S.T == 0) na += 1;
+        else nb += 1;
+    }
+    zonePostD(S, w, z, na, nb);
 }
 
 // SubZone state packed 4 bits per sub-zone k at bit 4k: controlling team + 1,
@@ -2646,7 +2616,7 @@ __global__ void __launch_bounds__(64) k_construct(DevState S, SceneDev sc, int32
     for (int k = 0; k < 6; k++) S.filtLast[(int64_t)w * 6 + k] = 0;
     S.worldCurr[w] = 1; // WorldCurriculum::FullMatch (sim.cpp:5959)
     const int32_t tc[3] = { tc0, tc1, tc2 };
-    initWorldD(S, sc, w, true, tc);
+    initWorldD(S, sc, w, true, tc, MemAgents{ S, g0, sc.aSpawns, sc.bSpawns, sc.commonRespawns }, DrawnKeys{}, SpawnApply{});
     S.matchValid[w] = 0; // matchID = ~0 after construction (sim.cpp:5971)
     S.evLogged[w] = 0;
     S.evMask[w] = 0;
@@ -2685,7 +2655,7 @@ __global__ void __launch_bounds__(64) k_reset_only(DevState S, SceneDev sc)
 {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= S.W) return;
-    resetSystemD(S, sc, w);
+    resetSystemD(S, sc, w, MemAgents{ S, (int64_t)w * S.N, sc.aSpawns, sc.bSpawns, sc.commonRespawns }, DrawnKeys{}, SpawnApply{});
 }
 
 // The Step graph up to and including resetSystem, one workgroup per tile of
@@ -2722,16 +2692,48 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
 // holds floor(kSimBlock / N) whole worlds, lane = agent, phases separated
 // by workgroup barriers.
 constexpr int kSimBlock = 128;
-// k_sim's dynamic LDS: the BVH image, which the phases after the last BVH
-// use reuse (the reset's draw keys, kPreDraws + 1 per lane, then the spawn
-// records, kSpawnRec floats per lane), then the spawn lists.
+// k_sim's dynamic LDS: the BVH image, then the spawn lists.  The phases
+// after the last BVH use reuse the image's bytes: the reset's draw keys
+// (kPreDraws + 1 per lane) from its start, the spawn records (kSpawnRec
+// floats per lane) behind them, and respawnCoopD's scratch (4 floats per
+// lane) in the keys' place, which the reset fills only later.
 constexpr size_t kSimKeyBytes = (size_t)kSimBlock * (kPreDraws + 1) * sizeof(RandKey);
+constexpr size_t kSimRecOffset = kSimKeyBytes;
+constexpr size_t kSimRecBytes = (size_t)kSimBlock * kSpawnRec * sizeof(float);
+constexpr size_t kSimCoopBytes = (size_t)kSimBlock * 4 * sizeof(float);
+constexpr size_t kSimReuseBytes = kSimRecOffset + kSimRecBytes;
+static_assert(kSimCoopBytes <= kSimRecOffset, "respawnCoopD's scratch must end below the spawn records");
+static_assert(kSimReuseBytes == kSimKeyBytes + kSimRecBytes, "the keys and the records are all that reuses the BVH image");
 __host__ __device__ size_t simSpawnOffset(const SceneDev &sc)
 {
     const size_t bvh = (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16;
-    const size_t reuse = kSimKeyBytes + (size_t)kSimBlock * kSpawnRec * 4;
-    return ((bvh > reuse ? bvh : reuse) + 15) & ~(size_t)15;
+    return ((bvh > kSimReuseBytes ? bvh : kSimReuseBytes) + 15) & ~(size_t)15;
 }
+
+// k_sim's per-agent floats for the world lane (static LDS), one struct per
+// phase in one union: a phase's writes begin after the barrier that ends the
+// previous phase's reads.  Integers are stored as float bits.
+struct SimFireLds { float px[kSimBlock], py[kSimBlock], pz[kSimBlock], hp[kSimBlock], respawn[kSimBlock]; };
+// (also the crumbs' positions in pos and the reset's flags in flags)
+struct SimRespawnLds { float pos[3 * kSimBlock], flags[kSimBlock]; };
+struct SimCrumbLds { float4 buf[2 * kSimBlock]; };
+struct SimGoalLds { float dist[6 * kSimBlock]; };
+// (team: 2 per world, at most kSimBlock / 2 worlds as N >= 2)
+struct SimRewardLds { float rew[kSimBlock], team[kSimBlock]; };
+union SimLds {
+    SimFireLds fire;
+    SimRespawnLds respawn;
+    SimCrumbLds crumb;
+    SimGoalLds goal;
+    SimRewardLds reward;
+};
+static_assert(sizeof(SimFireLds) <= sizeof(SimLds) && sizeof(SimRespawnLds) <= sizeof(SimLds) &&
+                  sizeof(SimCrumbLds) <= sizeof(SimLds) && sizeof(SimGoalLds) <= sizeof(SimLds) &&
+                  sizeof(SimRewardLds) <= sizeof(SimLds),
+              "every phase fits the union");
+static_assert(sizeof(SimLds) == (size_t)kSimBlock * 8 * sizeof(float), "k_sim's static LDS stays at 8 floats per lane");
+// the reset's flags are written while the world lanes still read the rewards
+static_assert(offsetof(SimRespawnLds, flags) >= sizeof(SimRewardLds), "reset flags must not overlap the rewards");
 
 __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, int i);
 
@@ -2765,7 +2767,7 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
     // the respawn (after fireD) unless the flank reward traces rays later,
     // the reset (last phase) unless curriculum snapshots rewrite agents after
     // the spawn (then the world lane stores everything itself)
-    float *const spawnRec = reinterpret_cast<float *>(smem + kSimKeyBytes);
+    float *const spawnRec = reinterpret_cast<float *>(smem + kSimRecOffset);
     const bool recRespawn = !sc.flank && !(sc.simFlags & kFlagNoRespawn);
     const bool recReset = sc.numSnapshots == 0;
     const int N = S.N;
@@ -2778,12 +2780,12 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
     const int64_t g = (int64_t)w * N + i;
 
     __shared__ uint8_t agentB[kSimBlock]; // per-agent bytes for the world lane (alive, done)
-    // per-agent floats for the world lane, reused by phase: respawn
-    // (positions [3 * kSimBlock], flags), crumb rounds (2 float4 per lane),
-    // goal distances (stride 6), rewards, reset (flags)
-    __shared__ __attribute__((aligned(16))) float goalDist[kSimBlock * 8];
-    float *const sposL = goalDist;
-    float *const sflagL = goalDist + 3 * kSimBlock;
+    __shared__ SimLds lds;
+    float *const sposL = lds.respawn.pos;
+    float *const sflagL = lds.respawn.flags;
+    // my world's agents in LDS for the world lane's respawn and reset (which
+    // reads only the flags, resetPreD's by then, and the lists)
+    const LdsAgents worldL = { &sposL[3 * wl * N], &agentB[wl * N], &sflagL[wl * N], tabA, tabB, tabC };
     if (act && sc.eventsOn) { // ClearTmpNode<GameEventEntity> at step start (sim.cpp:5344)
         mpenv_game_event *ev = &S.events[(int64_t)w * S.evStride];
         ev[2 * i].type = 0;
@@ -2801,21 +2803,19 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
         {
             // every agent's own fire inputs in one round of loads; the
             // world's positions, hp and respawn counters (the shots' capsule
-            // tests and targets) through LDS (goalDist's, free until the
-            // respawn below)
-            float *const fpx = goalDist, *const fpy = goalDist + kSimBlock, *const fpz = goalDist + 2 * kSimBlock;
-            float *const fhp = goalDist + 3 * kSimBlock, *const frs = goalDist + 4 * kSimBlock;
+            // tests and targets) through LDS
+            SimFireLds &f = lds.fire;
             FireIn fin;
             if (act) {
                 fin = fireLoadD(S, g);
-                fpx[threadIdx.x] = fin.pos.x;
-                fpy[threadIdx.x] = fin.pos.y;
-                fpz[threadIdx.x] = fin.pos.z;
-                fhp[threadIdx.x] = fin.hp;
-                frs[threadIdx.x] = __int_as_float(fin.respawn);
+                f.px[threadIdx.x] = fin.pos.x;
+                f.py[threadIdx.x] = fin.pos.y;
+                f.pz[threadIdx.x] = fin.pos.z;
+                f.hp[threadIdx.x] = fin.hp;
+                f.respawn[threadIdx.x] = __int_as_float(fin.respawn);
             }
             __syncthreads();
-            if (act) fireD(S, sc, bvh, w, i, fin, fpx, fpy, fpz, fhp, frs, wl * N);
+            if (act) fireD(S, sc, bvh, w, i, fin, f.px, f.py, f.pz, f.hp, f.respawn, wl * N);
         }
         __syncthreads();
         // the agents' alive states, positions and flags go to the world
@@ -2835,24 +2835,17 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
         const bool coopRespawn = recRespawn && sc.numCommon > 0 && sc.numCommon <= 64 &&
                                  !(sc.simFlags & kFlagNavmeshSpawn);
         if (coopRespawn)
-            respawnCoopD(S, sc, w, i, wl, act,
-                         SpawnLds{ &sposL[3 * wl * N], &agentB[wl * N], &sflagL[wl * N], tabA, tabB, tabC },
-                         spawnRec + wl * N * kSpawnRec, reinterpret_cast<float *>(smem));
+            respawnCoopD(S, sc, w, i, wl, act, worldL, spawnRec + wl * N * kSpawnRec, reinterpret_cast<float *>(smem));
         else if (wlane && !(sc.simFlags & kFlagNoRespawn)) {
-            uint32_t dead = 0;
-            #pragma unroll 1
-            for (int k = 0; k < N; k++)
-                if (!agentB[wl * N + k]) dead |= 1u << k;
-            spawnAgentsD(S, sc, w, true, nullptr, dead,
-                         SpawnLds{ &sposL[3 * wl * N], &agentB[wl * N], &sflagL[wl * N], tabA, tabB, tabC },
-                         recRespawn ? spawnRec + wl * N * kSpawnRec : nullptr);
+            if (recRespawn) respawnSerialD(S, sc, w, worldL, SpawnRecord{ spawnRec + wl * N * kSpawnRec });
+            else respawnSerialD(S, sc, w, worldL, SpawnApply{});
         }
         if (recRespawn) {
             // the respawned agents' own stores, from the world lane's records
             __syncthreads();
             if (dead_now) {
                 const ZoneBox zb = zoneBoxD(sc, S.curZone[w]);
-                spawnApplyRecD(S, sc, g, true, spawnRec + threadIdx.x * kSpawnRec, __float_as_int(sflagL[threadIdx.x]), zb);
+                spawnApplyD(S, sc, g, true, ldSpawnRecD(spawnRec + threadIdx.x * kSpawnRec), __float_as_int(sflagL[threadIdx.x]), zb);
             }
         }
         __syncthreads();
@@ -2876,7 +2869,7 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
                 if (sc.recordOn) recordAgentD(S, w, i);
                 const bool req = leaveBreadcrumbAgentD(S, w, g);
                 zoneIn[threadIdx.x] = (zin ? 1 : 0) | (req ? 2 : 0);
-                // the position a requested crumb takes (sposL's LDS, free here)
+                // the position a requested crumb takes
                 const Vec3 p = ldPos(S, g);
                 sposL[3 * threadIdx.x] = p.x;
                 sposL[3 * threadIdx.x + 1] = p.y;
@@ -2902,28 +2895,26 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
         }
         __syncthreads();
         // accumulateBreadcrumbPenalties and the crumbs' decay (the end of
-        // that system), in rounds over LDS (goalDist's, free until below)
-        crumbRoundsD(S, w, i, act, wl, reinterpret_cast<float4 *>(goalDist));
+        // that system), in rounds over LDS
+        crumbRoundsD(S, w, i, act, wl, lds.crumb.buf);
     }
     // zoneMatchInfoSystem's per-agent reads, one lane per agent (the world
     // lane would otherwise walk them serially)
     __shared__ uint8_t matchBits[kSimBlock];
     if (act) {
         matchBits[threadIdx.x] = (uint8_t)matchAgentBitsD(S, w, i);
-        goalDistAgentD(S, sc, w, i, ldPos(S, g), &goalDist[threadIdx.x * 6]);
+        goalDistAgentD(S, sc, w, i, ldPos(S, g), &lds.goal.dist[threadIdx.x * 6]);
     }
     __syncthreads();
     if (wlane) {
         zoneMatchInfoD(S, sc, w, &matchBits[wl * N]);
-        goalRegionsD(S, sc, w, &goalDist[wl * N * 6]);
+        goalRegionsD(S, sc, w, &lds.goal.dist[wl * N * 6]);
     }
     __syncthreads();
     // rewards and done flags go to the world lane through LDS (rewL, agentB)
     // instead of being read back from memory one agent at a time
-    // (in goalDist's LDS, whose last reader finished before the barrier above;
-    // teamL: 2 per world, at most kSimBlock / 2 worlds as N >= 2)
-    float *const rewL = goalDist;
-    float *const teamL = goalDist + kSimBlock;
+    float *const rewL = lds.reward.rew;
+    float *const teamL = lds.reward.team;
     if (act) {
         exploreVisitedD(S, w, g);
         if (sc.flank && sc.task == MPENV_TASK_ZONE) rewL[threadIdx.x] = flankRewardD(S, sc, bvh, w, i);
@@ -2979,15 +2970,15 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
             S.ftReward[(int64_t)w * 2 + t] = r;
             S.ftDone[(int64_t)w * 2 + t] = done ? 1 : 0;
         }
-        resetSystemD(S, sc, w, pre, SpawnLds{ nullptr, nullptr, &sflagL[wl * N], tabA, tabB, tabC },
-                     recReset ? spawnRec + wl * N * kSpawnRec : nullptr);
+        if (recReset) resetSystemD(S, sc, w, worldL, PreparedKeys{ pre }, SpawnRecord{ spawnRec + wl * N * kSpawnRec });
+        else resetSystemD(S, sc, w, worldL, PreparedKeys{ pre }, SpawnApply{});
     }
     if (recReset) {
         // the reset agents' own stores, from the world lane's records
         __syncthreads();
         if (resetting) {
             const ZoneBox zb = zoneBoxD(sc, S.curZone[w]);
-            spawnApplyRecD(S, sc, g, false, spawnRec + threadIdx.x * kSpawnRec, __float_as_int(sflagL[threadIdx.x]), zb);
+            spawnApplyD(S, sc, g, false, ldSpawnRecD(spawnRec + threadIdx.x * kSpawnRec), __float_as_int(sflagL[threadIdx.x]), zb);
             resetAgentTailD(S, g);
         }
     }

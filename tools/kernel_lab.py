@@ -41,7 +41,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # -DMPENV_LAB_SIM_SKIP=bits to switch phases off (wrong results by design),
 # -DMPENV_SIM_WPE=n for the waves-per-SIMD target, -DMPENV_SIM_BLOCK=n for
 # the block size.
-KSIM_SKIP = [("fireD(", 1), ("spawnAgentsD(", 2), ("zoneMatchInfoD(", 8), ("goalRegionsD(", 16),
+KSIM_SKIP = [("fireD(", 1), ("respawnSerialD(", 2), ("zoneMatchInfoD(", 8), ("goalRegionsD(", 16),
              ("resetSystemD(", 128), ("appendCrumbsD(", 256), ("crumbRoundsD(", 512),
              ("exploreVisitedD(", 1024)]
 
