@@ -426,6 +426,57 @@ int mpenv_combat_actions(mpenv_manager *mgr, const int32_t *tape_device, int32_t
 int mpenv_debug_trace_rays(mpenv_manager *mgr, const float *o_device, const float *d_device, int32_t n,
                            int32_t mode, float *t_device, int32_t *hit_device, void *hip_stream);
 
+/* Test hook (no reference counterpart): the device geometry queries of the
+ * step kernels, one query per thread over caller buffers in device memory.
+ * The kernel calls the step kernels' own device functions (geom_dev.h and
+ * the cast wrappers of kernels.hip) on an LDS image staged by the same
+ * staging function, with the same LDS size, as the kernel it stands in for.
+ * It proves the shortcut arguments of those functions (bounded searches,
+ * early exits, hints, culls, shared traversals, dealt casts) on inputs a
+ * rollout almost never produces.  It does not prove the step kernels' own
+ * code generation: the functions are force-inlined and compiled again into
+ * the hook's kernel; whole-step parity keeps covering that.
+ *
+ * Which tree each query walks: the lidar ray walks the lidar tree's octant
+ * images (k_lidar); the world ray (shots), line of sight (k_vis, sub 0, and
+ * the flank reward's, sub 1) and the sphere casts walk the collision tree in
+ * slot order, as the reference's traceRayAgainstWorld, isAgentVisible and
+ * sphereCast walk its one tree.
+ *
+ * Unused pointers may be null.  n queries; MPENV_GEOM_STUCK: n lanes, a
+ * multiple of 64, each run of 64 one wave. */
+enum {
+    MPENV_GEOM_LIDAR_RAY = 0, /* bvhTraceRayT on the octant image of rayOctant(d), as k_lidar: t (FLT_MAX on a miss), i0 = hit */
+    MPENV_GEOM_WORLD_RAY = 1, /* traceWorldD (collision tree): caps, sel = self (-1 none); i0 = hit, t (FLT_MAX on a miss), i1 = entity */
+    MPENV_GEOM_SIGHT = 2,     /* sub 0: visibleQuickD then visibleFullD as k_vis chains them, hint read and
+                               * written back; sub 1: visibleRayD without a hint (k_sim's flank use).
+                               * sel = target; i0 = seen */
+    MPENV_GEOM_CASTS = 3,     /* sub 0 bvhSphereCastD (full); 1 castNearD(bound); 2 castNear2D(z1, act1 = sel,
+                               * bound): t [n][2], normal [n][2][3], cast 1 left at (FLT_MAX, 0) when not
+                               * run; 3 castFirstNearD(bound): t only.  t [n], normal [n][3] otherwise */
+    MPENV_GEOM_STUCK = 4      /* stuckCastsD as applyVelocityD calls it: sel bit 0 = active (inactive lanes have
+                               * returned before the call, as in k_move), bit 1 = need; o = x, d = v_norm,
+                               * bound = low_check; every active lane reads its hd4 from t [n][4] before
+                               * the call and stores it after */
+};
+typedef struct mpenv_geom_queries {
+    const float *o;       /* [n][3] origins */
+    const float *d;       /* [n][3] directions */
+    const float *caps;    /* [n][num_caps][3] capsule bases (agent positions) of each query's world */
+    const int32_t *sel;   /* [n] per mode: self / target / act1 / lane flags */
+    const float *bound;   /* [n] cast bound / low_check */
+    const float *z1;      /* [n] castNear2D's second origin z */
+    uint16_t *hint;       /* [n] occluder hints, in and out (sight sub 0) */
+    float *t;             /* outputs, see the modes */
+    float *normal;
+    int32_t *i0;
+    int32_t *i1;
+    int32_t num_caps;     /* 1..12 */
+    int32_t sub;
+} mpenv_geom_queries;
+int mpenv_debug_geom_queries(mpenv_manager *mgr, int32_t mode, int32_t n, const mpenv_geom_queries *q,
+                             void *hip_stream);
+
 /* Extension, the learner exchange's compact wire format (DESIGN.md §6;
  * replaces shipping the trainInterface outputs of mgr.cpp:2383-2431 as they
  * are exported, 3,924 B per agent, with ~477 B per agent + 160 B per world).

@@ -299,7 +299,6 @@ struct SceneDev {
     const SceneTables *tab; // device copy of the arrays below (set after scene upload)
     const BVHNode *nodes;
     const BVHNode *octNodes; // [8][numLidarNodes] octant node images of the lidar tree (scene.h octantNodeImages)
-    const BVHNode *lidarNodes; // the lidar tree in slot order (k_vis)
     const float *lidarVerts; // the lidar tree's triangles, 3 floats per vertex (scene.h Scene::lidarVerts)
     int32_t numLidarNodes, numLidarVerts;
     const float *verts;     // 3 floats per vertex, 3 vertices per triangle
@@ -389,6 +388,8 @@ int launchLidar(const DevState &s, const SceneDev &sc, int iters, void *stream);
 int computeZoneGoalTris(const SceneDev &sc, int32_t *dev_scratch, int32_t *host_out, void *stream);
 int launchTraceRays(const SceneDev &sc, const float *o, const float *d, int n, int mode, float *t, int32_t *hit,
                     void *stream);
+// mpenv_debug_geom_queries (include/mpenv.h)
+int launchGeomQueries(const SceneDev &sc, int mode, int n, const mpenv_geom_queries &q, void *stream);
 int launchDebugGather(const DevState &s, float *af, int32_t *ai, int32_t *wi, float *wf, uint32_t *explore,
                       float *crumbs, void *stream);
 int launchFillActions(const DevState &s, const int32_t *src6, void *stream);

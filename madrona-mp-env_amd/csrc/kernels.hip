@@ -3109,7 +3109,7 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
     const int64_t wave = ((int64_t)xcdBlockId() * blockDim.x + threadIdx.x) >> 6;
     const int64_t agent0 = (((int64_t)xcdBlockId() * blockDim.x) >> 6) * apw; // first agent of the block
     const int nsMax = visStageAgents(T, N);
-    float *st = (float *)(smem + (size_t)sc.numLidarNodes * 64 + (size_t)sc.numLidarVerts * 16);
+    float *st = (float *)(smem + (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16);
     const int64_t s0 = (agent0 / N) * N;
     {
         const int64_t a_hi = min(S.A, agent0 + (int64_t)(kBlock / 64) * apw);
@@ -3127,7 +3127,11 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
             st[8 * nsMax + k] = S.alive[g];
         }
     }
-    const LBVH bvh = stageBVH(smem, sc, true); // the lidar tree; barrier
+    // The collision tree, as isAgentVisible walks it (the reference has one
+    // tree): which triangles a traversal reaches depends on the tree for rays
+    // along a zero-margin child box face, so another tree can answer
+    // differently (DESIGN.md section 2 definition 4).  Barrier.
+    const LBVH bvh = stageBVH(smem, sc);
     auto sPos = [&](int64_t g) {
         const int l = (int)(g - s0);
         return v3(st[0 * nsMax + l], st[1 * nsMax + l], st[2 * nsMax + l]);
@@ -3211,7 +3215,7 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
     // again so B2's traversals run in dense waves (a wave of mixed rays
     // otherwise idles all but its few traversing lanes).
     const uint32_t total = nrays;
-    const uint32_t numTris = (uint32_t)(sc.numLidarVerts / 3);
+    const uint32_t numTris = (uint32_t)(sc.numVerts / 3);
     // the occluder hint stores triangle ids as u16 with 0xffff = none: off
     // for scenes of 65,535 triangles or more
     const bool hints = numTris < 0xffffu;
@@ -4295,6 +4299,127 @@ int launchTraceRays(const SceneDev &sc, const float *o, const float *d, int n, i
     return check(hipGetLastError());
 }
 
+// Test hook (mpenv_debug_geom_queries, include/mpenv.h): one geometry query
+// per thread through the step kernels' own device functions, on the LDS image
+// of the kernel each mode stands in for (k_lidar / k_sim / k_vis / k_move).
+// The functions are force-inlined, so this is a second compilation of them:
+// it checks their shortcut arguments on chosen inputs, not the step kernels'
+// code generation (whole-step parity covers that).
+template <int kMode>
+__global__ void __launch_bounds__(kBlock) k_geom_queries(SceneDev sc, mpenv_geom_queries q, int n)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    LBVH bvh;
+    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) bvh = stageBVHOct(smem, sc);
+    else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) bvh = stageBVH(smem, sc);
+    else if constexpr (kMode == MPENV_GEOM_SIGHT) bvh = stageBVH(smem, sc);
+    else bvh = stageBVHSphere(smem, sc);
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const Vec3 org = v3(q.o[3 * r], q.o[3 * r + 1], q.o[3 * r + 2]);
+    const Vec3 dir = v3(q.d[3 * r], q.d[3 * r + 1], q.d[3 * r + 2]);
+    const int N = q.num_caps;
+    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) {
+        // as k_lidar forms `ob`
+        LBVH ob = bvh;
+        ob.nodes = reinterpret_cast<const MP_LDS BVHNode *>(reinterpret_cast<const MP_LDS uint4 *>(bvh.nodes) +
+                                                             rayOctant(dir) * sc.numLidarNodes * kOctNodeQ);
+        float tb;
+        const bool hit = bvhTraceRayT<false, kOctNodeQ, true, true>(ob, org, dir, tb, kFltMax, 0.f);
+        q.t[r] = tb;
+        q.i0[r] = hit ? 1 : 0;
+    } else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) {
+        float cx[12], cy[12], cz[12]; // the query's world as position columns
+        for (int j = 0; j < N; j++) {
+            const float *cp = q.caps + ((size_t)r * N + j) * 3;
+            cx[j] = cp[0]; cy[j] = cp[1]; cz[j] = cp[2];
+        }
+        const WorldHit h = traceWorldD(bvh, cx, cy, cz, 0, N, org, dir, q.sel[r]);
+        q.i0[r] = h.hit ? 1 : 0;
+        q.t[r] = h.t;
+        q.i1[r] = h.entity;
+    } else if constexpr (kMode == MPENV_GEOM_SIGHT) {
+        const int target = q.sel[r];
+        bool seen;
+        if (q.sub == 0) {
+            // k_vis phase B: B1 on every ray, B2 on the unresolved ones
+            const uint32_t numTris = (uint32_t)(sc.numVerts / 3);
+            const bool hints = numTris < 0xffffu;
+            auto capsule = [&](int j) {
+                const float *cp = q.caps + ((size_t)r * N + j) * 3;
+                return v3(cp[0], cp[1], cp[2]);
+            };
+            float t_c;
+            seen = false;
+            if (!visibleQuickD(bvh, capsule, org, dir, target, hints ? q.hint + r : nullptr, numTris, t_c))
+                seen = visibleFullD(bvh, capsule, N, org, dir, target, t_c, hints ? q.hint + r : nullptr);
+        } else {
+            float cx[12], cy[12], cz[12];
+            for (int j = 0; j < N; j++) {
+                const float *cp = q.caps + ((size_t)r * N + j) * 3;
+                cx[j] = cp[0]; cy[j] = cp[1]; cz[j] = cp[2];
+            }
+            seen = visibleRayD(bvh, cx, cy, cz, 0, N, org, dir, target);
+        }
+        q.i0[r] = seen ? 1 : 0;
+    } else if constexpr (kMode == MPENV_GEOM_CASTS) {
+        if (q.sub == 2) {
+            SphereHit h0, h1;
+            h1.t = kFltMax;
+            h1.n = v3(0.f, 0.f, 0.f);
+            castNear2D(bvh, sc, org, q.z1[r], dir, q.bound[r], q.sel[r] != 0, h0, h1);
+            q.t[2 * r] = h0.t;
+            q.t[2 * r + 1] = h1.t;
+            float *np = q.normal + (size_t)r * 6;
+            np[0] = h0.n.x; np[1] = h0.n.y; np[2] = h0.n.z;
+            np[3] = h1.n.x; np[4] = h1.n.y; np[5] = h1.n.z;
+        } else if (q.sub == 3) {
+            q.t[r] = castFirstNearD(bvh, sc, org, dir, q.bound[r]);
+        } else {
+            const SphereHit h = q.sub == 0 ? bvhSphereCastD(bvh, org, dir, kSphereR)
+                                           : castNearD(bvh, sc, org, dir, q.bound[r]);
+            q.t[r] = h.t;
+            q.normal[3 * r] = h.n.x; q.normal[3 * r + 1] = h.n.y; q.normal[3 * r + 2] = h.n.z;
+        }
+    } else {
+        // applyVelocityD's call: lanes that left k_move early are gone, the
+        // rest call with or without `need`
+        const int flags = q.sel[r];
+        if (!(flags & 1)) return;
+        float hd4[4];
+        for (int k = 0; k < 4; k++) hd4[k] = q.t[4 * r + k];
+        stuckCastsD(bvh, (flags & 2) != 0, org, dir, q.bound[r], hd4);
+        for (int k = 0; k < 4; k++) q.t[4 * r + k] = hd4[k];
+    }
+}
+
+int launchGeomQueries(const SceneDev &sc, int mode, int n, const mpenv_geom_queries &q, void *stream)
+{
+    if (n <= 0) return 0;
+    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    switch (mode) {
+    case MPENV_GEOM_LIDAR_RAY:
+        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_LIDAR_RAY>, grid, block, bvhLdsBytesOct(sc), st, sc, q, n);
+        break;
+    case MPENV_GEOM_WORLD_RAY:
+        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_WORLD_RAY>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
+        break;
+    case MPENV_GEOM_SIGHT:
+        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_SIGHT>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
+        break;
+    case MPENV_GEOM_CASTS:
+        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_CASTS>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
+        break;
+    case MPENV_GEOM_STUCK:
+        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_STUCK>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
+        break;
+    default:
+        return -1;
+    }
+    return check(hipGetLastError());
+}
+
 // Debug gather of internal state into the MPENV_EXPORT_DEBUG_* layouts.
 __global__ void __launch_bounds__(256) k_debug(DevState S, float *af, int32_t *ai, int32_t *wi, float *wf,
                                                uint32_t *explore, float *crumbs)
@@ -4455,7 +4580,6 @@ size_t bvhLdsBytesSphere(const SceneDev &sc)
     return bvhLdsBytes(sc) + (size_t)(sc.numVerts / 3) * 32 + (size_t)sc.numNodes * kSNodeFloats * 4;
 }
 
-
 size_t bvhLdsBytesOct(const SceneDev &sc)
 {
     return (size_t)sc.numLidarNodes * 16 * kOctNodeQ * 8 + (size_t)sc.numLidarVerts * 16 * 3;
@@ -4509,8 +4633,8 @@ int launchVisibility(const DevState &s, const SceneDev &sc, void *stream)
     const int64_t waves = (s.A + (64 / s.T) - 1) / (64 / s.T);
     const int blocks = (int)((waves * 64 + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_vis, dim3(blocks), dim3(kBlock),
-                       (size_t)sc.numLidarNodes * 64 + (size_t)sc.numLidarVerts * 16 +
-                           (size_t)kVisStageCols * 4 * visStageAgents(s.T, s.N), (hipStream_t)stream, s, sc);
+                       bvhLdsBytes(sc) + (size_t)kVisStageCols * 4 * visStageAgents(s.T, s.N),
+                       (hipStream_t)stream, s, sc);
     return check(hipGetLastError());
 }
 

@@ -592,9 +592,6 @@ static void buildSceneDev(mpenv_manager &m)
         BVHNode *d_oct = m.alloc<BVHNode>(oct.size());
         m.upload(d_oct, oct.data(), sizeof(BVHNode) * oct.size());
         sc.octNodes = d_oct;
-        BVHNode *d_ln = m.alloc<BVHNode>(s.lidarNodes.size());
-        m.upload(d_ln, s.lidarNodes.data(), sizeof(BVHNode) * s.lidarNodes.size());
-        sc.lidarNodes = d_ln;
         float *d_lv = m.alloc<float>(s.lidarVerts.size() * 3);
         m.upload(d_lv, s.lidarVerts.data(), sizeof(float) * 3 * s.lidarVerts.size());
         sc.lidarVerts = d_lv;
@@ -1262,6 +1259,26 @@ int mpenv_debug_trace_rays(mpenv_manager *m, const float *o, const float *d, int
     hipStream_t st = stream ? (hipStream_t)stream : m->stream;
     if (launchTraceRays(m->sc, o, d, n, mode, t_out, hit_out, st) || hipStreamSynchronize(st) != hipSuccess)
         return fail(MPENV_ERR_HIP, "trace-ray launch failed");
+    return MPENV_OK;
+}
+
+int mpenv_debug_geom_queries(mpenv_manager *m, int32_t mode, int32_t n, const mpenv_geom_queries *q, void *stream)
+{
+    if (!m || !q || n < 0) return fail(MPENV_ERR_INVALID, "bad argument");
+    const bool caps = mode == MPENV_GEOM_WORLD_RAY || mode == MPENV_GEOM_SIGHT;
+    const bool casts = mode == MPENV_GEOM_CASTS;
+    bool ok = mode >= MPENV_GEOM_LIDAR_RAY && mode <= MPENV_GEOM_STUCK && q->o && q->d;
+    ok = ok && (mode == MPENV_GEOM_SIGHT || q->t) && (mode == MPENV_GEOM_CASTS || mode == MPENV_GEOM_STUCK || q->i0);
+    if (caps) ok = ok && q->caps && q->sel && q->num_caps >= 1 && q->num_caps <= 12;
+    if (mode == MPENV_GEOM_WORLD_RAY) ok = ok && q->i1;
+    if (mode == MPENV_GEOM_SIGHT) ok = ok && (q->sub == 1 || (q->sub == 0 && q->hint));
+    if (casts) ok = ok && q->sub >= 0 && q->sub <= 3 && (q->sub == 3 || q->normal) && (q->sub == 0 || q->bound) &&
+                     (q->sub != 2 || (q->z1 && q->sel));
+    if (mode == MPENV_GEOM_STUCK) ok = ok && q->sel && q->bound && n % 64 == 0;
+    if (!ok) return fail(MPENV_ERR_INVALID, "bad geometry query");
+    hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+    if (launchGeomQueries(m->sc, mode, n, *q, st) || hipStreamSynchronize(st) != hipSuccess)
+        return fail(MPENV_ERR_HIP, "geometry-query launch failed");
     return MPENV_OK;
 }
 

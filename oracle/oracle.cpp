@@ -3646,6 +3646,38 @@ void oracle_sphere_cast_batch(void *h, int32_t n, const float *org, const float 
     }
 }
 
+// traceRayAgainstWorld's body (utils.cpp:10-72) over caller rays and caller
+// capsule bases: the collision tree in slot order, then every capsule in
+// index order, none skipped.
+void oracle_trace_world_batch(void *h, int32_t n, const float *org, const float *d, const float *caps,
+                              int32_t num_caps, int32_t *hit_out, float *t_out, int32_t *entity_out)
+{
+    Oracle &o = *static_cast<Oracle *>(h);
+    for (int32_t k = 0; k < n; k++) {
+        const Vec3 ro = v3(org[3 * k], org[3 * k + 1], org[3 * k + 2]), rd = v3(d[3 * k], d[3 * k + 1], d[3 * k + 2]);
+        float min_hit_t = kFltMax;
+        float t_bvh;
+        bool hit = bvhTraceRay(o, ro, rd, &t_bvh);
+        if (hit) min_hit_t = t_bvh;
+        int hit_entity = -1;
+        for (int j = 0; j < num_caps; j++) {
+            const float *cp = caps + ((size_t)k * num_caps + j) * 3;
+            Vec3 capsule_origin = v3(cp[0], cp[1], cp[2]);
+            capsule_origin.z += kAgentRadius;
+            Vec3 translated = ro - capsule_origin;
+            float t = intersectRayZOriginCapsule(translated, rd, kAgentRadius, kStandHeight - 2.f * kAgentRadius);
+            if (t != 0 && t < min_hit_t) {
+                min_hit_t = t;
+                hit = true;
+                hit_entity = j;
+            }
+        }
+        hit_out[k] = hit ? 1 : 0;
+        t_out[k] = min_hit_t;
+        entity_out[k] = hit_entity;
+    }
+}
+
 int oracle_trace_ray_brute(void *h, const float *org, const float *d, float *t_out)
 {
     Oracle &o = *static_cast<Oracle *>(h);
@@ -3709,6 +3741,11 @@ void oracle_tape_actions(uint32_t seed, uint32_t step, uint32_t first_agent, int
 float oracle_capsule(const float *o, const float *d, float r, float h)
 {
     return intersectRayZOriginCapsule(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]), r, h);
+}
+
+void oracle_capsule_batch(int32_t n, const float *o, const float *d, float r, float h, float *t_out)
+{
+    for (int32_t k = 0; k < n; k++) t_out[k] = oracle_capsule(o + 3 * k, d + 3 * k, r, h);
 }
 
 } // extern "C"

@@ -105,6 +105,13 @@ void oracle_trace_ray_batch(void *h, int32_t n, const float *o, const float *d, 
  * t_max null = FLT_MAX): o, d, n_out [n][3]; normals are (0,0,0) on a miss. */
 void oracle_sphere_cast_batch(void *h, int32_t n, const float *o, const float *d, float r,
                               const float *t_max, float *t_out, float *n_out);
+/* n world rays, traceRayAgainstWorld's body (utils.cpp:10-72) over caller
+ * rays and caller capsule bases (caps [n][num_caps][3], agent positions):
+ * the collision tree in slot order, then every capsule in index order with
+ * no cull.  hit, t (FLT_MAX on a miss), entity (-1 none) [n]; a sight query
+ * sees its target when hit && entity == target (utils.cpp:218). */
+void oracle_trace_world_batch(void *h, int32_t n, const float *o, const float *d, const float *caps,
+                              int32_t num_caps, int32_t *hit_out, float *t_out, int32_t *entity_out);
 int oracle_trace_ray_brute(void *h, const float *o, const float *d, float *t_out);
 float oracle_sphere_cast_brute(void *h, const float *o, const float *d, float r);
 
@@ -115,6 +122,8 @@ void oracle_eval_math(int32_t fn, const float *in, const float *in2, float *out,
 void oracle_threefry(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t *out2);
 void oracle_tape_actions(uint32_t seed, uint32_t step, uint32_t first_agent, int32_t n, int32_t *out6);
 float oracle_capsule(const float *o, const float *d, float r, float h);
+/* oracle_capsule over n rays: o, d [n][3], t_out [n]. */
+void oracle_capsule_batch(int32_t n, const float *o, const float *d, float r, float h, float *t_out);
 
 #ifdef __cplusplus
 }

@@ -130,16 +130,17 @@ def casts(o, origins, dirs, t_max=None):
     return t, nrm
 
 
-def k_move_origins(n, rng):
+def k_move_origins(n, rng, worlds=8, steps=120):
     """Cast origins like applyVelocity's: agent positions from an oracle
-    rollout raised by the pose heights, and origins whose 2o lands near a
-    vertex (where the testVert quirk lives)."""
-    o = T.Oracle(8, 6)
+    rollout (`worlds` 6v6 worlds, `steps` tape steps) raised by the pose
+    heights, and origins whose 2o lands near a vertex (where the testVert
+    quirk lives)."""
+    o = T.Oracle(worlds, 6)
     o.put_ctrl([0, 1, 1])
     o.init()
     pos = []
-    for s in range(120):
-        o.set_actions(T.mpenv_tape.tape_actions(4321, s, 0, 8 * 12))
+    for s in range(steps):
+        o.set_actions(T.mpenv_tape.tape_actions(4321, s, 0, worlds * 12))
         o.step()
         if s % 6 == 5:
             pos.append(o.get("DEBUG_AGENT_F32")[:, :3].copy())
