@@ -265,6 +265,24 @@ def test_fork_continues_as_the_source_world_did(ts, W, groups):
     e.close()
 
 
+# World groups that start off a 4-agent boundary (tests/test_ragged_groups_gpu.py):
+# group starts at agents 6 and 18 (3v3 x 5 in three groups) and 10 (5v5 x 3 in
+# two), so a group's spans are 8 B off the 16-B alignment the whole batch has,
+# and the forks cross such a boundary.
+RAGGED = [(3, 5, 3), (5, 3, 2)]
+
+
+@pytest.mark.parametrize("ts,W,groups", RAGGED)
+@pytest.mark.parametrize("what", ["rewind", "fork"])
+def test_checkpoints_under_misaligned_world_groups(what, ts, W, groups):
+    starts = [W * i // groups * 2 * ts for i in range(1, groups)]
+    assert any(g0 % 4 for g0 in starts), starts
+    if what == "rewind":
+        test_rewind_and_replay_against_the_oracle(ts, W, groups)
+    else:
+        test_fork_continues_as_the_source_world_did(ts, W, groups)
+
+
 def test_refused_loads_write_nothing():
     ts, W = 3, 5
     e = engine_at(ts, W, 1, 3)
