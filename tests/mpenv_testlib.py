@@ -1,6 +1,7 @@
 """ctypes harness over the two C ABIs used by the tests.
 
-* libmpenv.so (the product, include/mpenv.h) — the gfx950 engine.
+* libmpenv.so (the product, include/mpenv.h) — the gfx950 engine, bound once
+  from the signature table of tests/mpenv_abi.py (lib_mpenv).
 * liboracle.so (oracle/oracle.h) — TEST INFRASTRUCTURE: the CPU restatement
   of the reference step used as the parity checker.
 
@@ -21,6 +22,7 @@ if PKG not in sys.path:
 
 import build_native  # noqa: E402
 import mpenv_tape  # noqa: E402
+from mpenv_abi import GeomQueries, MpenvConfig, bind  # noqa: E402,F401
 
 # ---------------------------------------------------------------- constants
 EXPORT = dict(
@@ -88,18 +90,6 @@ class OracleConfig(C.Structure):
     ]
 
 
-class MpenvConfig(C.Structure):
-    _fields_ = [
-        ("exec_mode", C.c_int32), ("gpu_id", C.c_int32), ("num_worlds", C.c_uint32),
-        ("rand_seed", C.c_uint32), ("auto_reset", C.c_int32), ("sim_flags", C.c_uint32),
-        ("task_type", C.c_int32), ("team_size", C.c_uint32), ("num_pbt_policies", C.c_uint32),
-        ("policy_history_size", C.c_uint32), ("scene_path", C.c_char_p), ("train_flank", C.c_int32),
-        ("replay_log_path", C.c_char_p), ("record_log_path", C.c_char_p),
-        ("event_log_path", C.c_char_p), ("curriculum_data_path", C.c_char_p),
-        ("world_id_offset", C.c_uint32),
-    ]
-
-
 _libs = {}
 
 
@@ -124,27 +114,7 @@ def lib_mpenv():
     if "mpenv" not in _libs:
         ensure_built()
         # MPENV_LIB: a kernel_lab variant of the library (development only)
-        lib = C.CDLL(os.environ.get("MPENV_LIB", build_native.LIB))
-        lib.mpenv_create.argtypes = [C.POINTER(MpenvConfig), C.POINTER(C.c_void_p)]
-        lib.mpenv_destroy.argtypes = [C.c_void_p]
-        for fn in ("mpenv_init", "mpenv_step"):
-            getattr(lib, fn).argtypes = [C.c_void_p]
-        lib.mpenv_step_async.argtypes = [C.c_void_p, C.c_void_p]
-        lib.mpenv_export_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p),
-                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                            C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        lib.mpenv_last_error.restype = C.c_char_p
-        lib.mpenv_scene_bvh.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        lib.mpenv_scene_navmesh.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
-                                            C.c_void_p]
-        lib.mpenv_trigger_reset.argtypes = [C.c_void_p, C.c_int32]
-        lib.mpenv_copy_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mpenv_set_hp.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.mpenv_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int32]
-        lib.mpenv_kernel_timings.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p),
-                                             C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-        _libs["mpenv"] = lib
+        _libs["mpenv"] = bind(C.CDLL(os.environ.get("MPENV_LIB", build_native.LIB)))
     return _libs["mpenv"]
 
 
@@ -212,8 +182,6 @@ def scene_bvh(scene=SCENE, lidar=False):
     """The collision tree, or (lidar=True) k_lidar's own tree."""
     lib = lib_mpenv()
     fn = lib.mpenv_scene_lidar_bvh if lidar else lib.mpenv_scene_bvh
-    fn.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32),
-                   C.POINTER(C.c_int32)]
     nn, nv, ms = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     rc = fn(scene.encode(), None, C.byref(nn), None, C.byref(nv), C.byref(ms))
     assert rc == 0, lib.mpenv_last_error()
@@ -423,6 +391,9 @@ class Engine:
     def __del__(self):
         self.close()
 
+    def _ok(self, rc):
+        assert rc == 0, self.lib.mpenv_last_error().decode()
+
     def desc(self, name):
         ptr, dt, nd, gpu = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
         dims = (C.c_int64 * 8)()
@@ -454,32 +425,90 @@ class Engine:
     def combat_actions(self, tape_dev, out_dev=None, mode=1):
         """mpenv_combat_actions: the device aim-bot over the tape rows at
         tape_dev ([A][6] i32), into out_dev or straight into the step inputs."""
-        self.lib.mpenv_combat_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        assert self.lib.mpenv_combat_actions(self.h, tape_dev, out_dev, mode, None) == 0, \
-            self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_combat_actions(self.h, tape_dev, out_dev, mode, None))
         if out_dev is not None:
             self.mem.hip.hipDeviceSynchronize()
 
     def set_world_groups(self, groups):
-        self.lib.mpenv_set_world_groups.argtypes = [C.c_void_p, C.c_int32]
-        assert self.lib.mpenv_set_world_groups(self.h, groups) == 0, self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_set_world_groups(self.h, groups))
 
     def enable_stats(self, on=True):
-        self.lib.mpenv_enable_stats.argtypes = [C.c_void_p, C.c_int32]
-        assert self.lib.mpenv_enable_stats(self.h, int(on)) == 0, self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_enable_stats(self.h, int(on)))
 
     def read_stats(self):
         """Workload counters (include/mpenv.h mpenv_read_stats)."""
-        self.lib.mpenv_read_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         v = np.zeros(10, np.uint64)
         assert self.lib.mpenv_read_stats(self.h, v.ctypes.data, 10) >= 0, self.lib.mpenv_last_error().decode()
         names = ("alive_agents", "los_pairs", "los_rays", "los_seen", "sphere_casts", "shot_rays",
                  "hit_agents", "kills", "lk_rows", "los_traced")
         return dict(zip(names, (int(x) for x in v)))
 
+    def graph_captures(self):
+        n = C.c_int64(-1)
+        self._ok(self.lib.mpenv_graph_captures(self.h, C.byref(n)))
+        return n.value
+
+    def graph_status(self):
+        """(graph_on, reason): 1 and "" while steps replay the captured graph."""
+        on, why = C.c_int32(-1), C.create_string_buffer(512)
+        self._ok(self.lib.mpenv_graph_status(self.h, C.byref(on), why, 512))
+        return on.value, why.value.decode()
+
+    def set_lidar_iters(self, n):
+        """The status code (out-of-range values are refused): callers assert."""
+        return self.lib.mpenv_set_lidar_iters(self.h, n)
+
+    # world checkpoints (mpenv_state_*); buffers are device addresses
+    def state_bytes(self):
+        n = C.c_int64()
+        self._ok(self.lib.mpenv_state_bytes(self.h, C.byref(n)))
+        return n.value
+
+    def state_save(self, buf, stream=None):
+        self._ok(self.lib.mpenv_state_save(self.h, buf, stream))
+
+    def state_load(self, buf, world_map=None, stream=None):
+        self._ok(self.lib.mpenv_state_load(self.h, buf, world_map, stream))
+
+    def state_error(self):
+        v = C.c_uint32(99)
+        self._ok(self.lib.mpenv_state_error(self.h, C.byref(v)))
+        return v.value
+
+    def new_state_blob(self):
+        """A device buffer for one snapshot, every byte 0xA5 (caller frees)."""
+        return self.mem.upload(np.full(self.state_bytes(), 0xA5, np.uint8))
+
+    # the learner exchange's wire format (mpenv_wire_*)
+    def wire_bytes(self, keyframe):
+        n = C.c_int64()
+        self._ok(self.lib.mpenv_wire_bytes(self.h, int(keyframe), C.byref(n)))
+        return n.value
+
+    def wire_pack(self, buf, keyframe):
+        self._ok(self.lib.mpenv_wire_pack(self.h, buf, int(keyframe), None))
+        self.mem.hip.hipDeviceSynchronize()
+
+    def wire_unpack(self, buf, keyframe):
+        self._ok(self.lib.mpenv_wire_unpack(self.h, buf, int(keyframe), None))
+        self.mem.hip.hipDeviceSynchronize()
+
+    def wire_error(self):
+        v = C.c_uint32(99)
+        self._ok(self.lib.mpenv_wire_error(self.h, C.byref(v)))
+        return v.value
+
+    # gpuStreamInit / gpuStreamStep on the caller's stream (a hipStream_t
+    # address) and pointer array (StreamBuffers.arrs[k])
+    def gpu_stream_init(self, stream, arr):
+        self._ok(self.lib.mpenv_gpu_stream_init(self.h, stream, arr))
+
+    def gpu_stream_step(self, stream, arr):
+        self._ok(self.lib.mpenv_gpu_stream_step(self.h, stream, arr))
+
     def copy_actions(self, dev_ptr):
         """Step inputs from device memory [A][6] i32 (gpuStreamStep's copy)."""
-        assert self.lib.mpenv_copy_actions(self.h, dev_ptr, None) == 0, self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_copy_actions(self.h, dev_ptr, None))
 
     def trigger_reset(self, w):
         assert self.lib.mpenv_trigger_reset(self.h, w) == 0
@@ -500,12 +529,91 @@ class Engine:
         self.put("PVP_DISCRETE_AIM_ACTION", acts6[:, 4:6])
 
     def init(self):
-        rc = self.lib.mpenv_init(self.h)
-        assert rc == 0, self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_init(self.h))
 
     def step(self):
-        rc = self.lib.mpenv_step(self.h)
-        assert rc == 0, self.lib.mpenv_last_error().decode()
+        self._ok(self.lib.mpenv_step(self.h))
+
+
+def state_dims(e):
+    """(num_worlds, team_size, spawn_track_len): what a snapshot's layout depends on."""
+    w, t, l = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    e._ok(e.lib.mpenv_state_dims(e.h, C.byref(w), C.byref(t), C.byref(l)))
+    return w.value, t.value, l.value
+
+
+def state_section(idx, W, team, track):
+    """mpenv_state_section as a dict, or None where the call is refused (one
+    past the last section, bad sizes); idx -1 describes the whole blob."""
+    name, off, nbytes = C.c_char_p(), C.c_int64(-1), C.c_int64(-1)
+    rb, kind, eid = C.c_int32(-1), C.c_int32(-9), C.c_int32(-9)
+    rc = lib_mpenv().mpenv_state_section(idx, W, team, track, C.byref(name), C.byref(off), C.byref(nbytes),
+                                         C.byref(rb), C.byref(kind), C.byref(eid))
+    if rc != 0:
+        return None
+    return dict(name=name.value.decode(), offset=off.value, bytes=nbytes.value, row_bytes=rb.value,
+                kind=kind.value, export_id=eid.value)
+
+
+def train_interface(e):
+    """[(is_output, name, export name, numpy dtype, shape)] in buffer order"""
+    lib = lib_mpenv()
+    ni, no = C.c_int32(), C.c_int32()
+    assert lib.mpenv_train_interface_size(C.byref(ni), C.byref(no)) == 0
+    inv = {v: k for k, v in EXPORT.items()}
+    out = []
+    for io, n in ((0, ni.value), (1, no.value)):
+        for k in range(n):
+            nm, eid = C.c_char_p(), C.c_int32()
+            assert lib.mpenv_train_interface_entry(io, k, C.byref(nm), C.byref(eid)) == 0
+            _, dt, shape = e.desc(inv[eid.value])
+            out.append((io, nm.value.decode(), inv[eid.value], dt, shape))
+    return out
+
+
+class StreamBuffers:
+    """Caller-owned torch buffers for Engine.gpu_stream_init / gpu_stream_step:
+    n_sets sets in train_interface order (ti), inputs zeros and outputs `fill`
+    (not zeros: every byte must be written), simCtrl [0, 1, 1].  sets[k][i] is
+    buffer i of set k, idx maps a name to i, arrs[k] is set k's pointer array.
+    A caller that swaps a buffer calls point() again."""
+
+    def __init__(self, e, n_sets=2, fill=7):
+        import torch
+
+        self.ti = train_interface(e)
+        self.idx = {nm: i for i, (_, nm, _, _, _) in enumerate(self.ti)}
+        self.sets = [[] for _ in range(n_sets)]
+        for io, _, _, dt, shape in self.ti:
+            tdt = {np.int32: torch.int32, np.float32: torch.float32}[dt]
+            for bs in self.sets:
+                bs.append(torch.full(shape, fill if io == 1 else 0, dtype=tdt, device="cuda"))
+        self.point()
+        for k in range(n_sets):
+            self.put(k, "simCtrl", np.array([0, 1, 1], np.int32))
+
+    def point(self):
+        self.arrs = [(C.c_void_p * len(bs))(*[b.data_ptr() for b in bs]) for bs in self.sets]
+
+    def put(self, k, name, arr):
+        import torch
+
+        t = self.sets[k][self.idx[name]]
+        t.copy_(torch.from_numpy(np.ascontiguousarray(arr)).view_as(t))
+
+    def set_actions(self, k, acts6):
+        self.put(k, "discrete", acts6[:, :4])
+        self.put(k, "aim", acts6[:, 4:6])
+
+
+def free_port():
+    import socket
+
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
 
 
 def explore_visited(sim):

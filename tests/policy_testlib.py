@@ -207,20 +207,8 @@ def engine_obs(engine):
     return {k: engine.get(name) for k, name in ENGINE_INPUTS.items()}
 
 
-def policy_lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_policy_check.argtypes = [C.c_char_p]
-    lib.mpenv_policy_load.argtypes = [C.c_void_p, C.c_char_p]
-    lib.mpenv_policy_unload.argtypes = [C.c_void_p]
-    lib.mpenv_policy_loaded.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-    lib.mpenv_policy_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_debug_policy_dense.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                             C.c_void_p, C.c_void_p]
-    return lib
-
-
 def policy_check(dirname):
     """(return code, message) of mpenv_policy_check."""
-    lib = policy_lib()
+    lib = T.lib_mpenv()
     rc = lib.mpenv_policy_check(os.fsencode(str(dirname)))
     return rc, (lib.mpenv_last_error().decode() if rc else "")

@@ -10,6 +10,7 @@ import pytest
 import mpenv_testlib as T
 
 HEADER = os.path.join(T.ROOT, "include", "mpenv.h")
+HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def declared_functions():
@@ -25,6 +26,44 @@ def test_header_declares_the_manager_surface():
               "mpenv_trigger_reset", "mpenv_set_pvp_action", "mpenv_set_hp",
               "mpenv_train_interface_size", "mpenv_train_interface_entry", "mpenv_copy_actions"):
         assert f in fns, f
+
+
+def declarations():
+    """{function: (return type, [parameter types])} as the header spells
+    them, a pointer or array parameter reduced to "*"."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    pattern = r"^([A-Za-z_][\w ]*?[ *]+)(mpenv_[a-z0-9_]+)\s*\(([^()]*)\)\s*;"  # type name(params); over 1-3 lines
+    for ret, name, params in re.findall(pattern, text, flags=re.M):
+        kinds = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = p.replace("const", " ").split()
+            kinds.append("*" if "*" in p or "[" in p else " ".join(words[:-1]))
+        out[name] = (" ".join(ret.replace("*", " * ").split()), kinds)
+    return out
+
+
+def test_binding_table_matches_header():
+    """tests/mpenv_abi.py SIGNATURES, the one ctypes binding every test and
+    tool calls through, against include/mpenv.h: the same functions, the same
+    number of parameters, every pointer pointer-sized and every integer of the
+    declared width (ctypes would otherwise pass a 64-bit address as a C int)."""
+    from mpenv_abi import SIGNATURES
+
+    decl = declarations()
+    assert sorted(decl) == declared_functions()  # the parser saw every declaration
+    assert sorted(SIGNATURES) == sorted(decl), set(SIGNATURES) ^ set(decl)
+    returns = {"int": C.c_int32, "int32_t": C.c_int32, "int64_t": C.c_int64, "void": None, "const char *": C.c_char_p}
+    values = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "size_t": C.c_size_t}
+    for name, (ret, kinds) in decl.items():
+        restype, argtypes = SIGNATURES[name]
+        assert restype is returns[ret], (name, ret, restype)
+        assert len(argtypes) == len(kinds), (name, kinds, argtypes)
+        for k, (kind, at) in enumerate(zip(kinds, argtypes)):
+            if kind == "*":
+                assert at in (C.c_void_p, C.c_char_p) or issubclass(at, C._Pointer), (name, k, at)
+            else:
+                assert at is values[kind], (name, k, kind, at)
 
 
 def test_library_exports_every_declared_symbol():
@@ -174,10 +213,12 @@ def test_product_kernels_carry_no_lab_switches_and_lab_patches_apply(tmp_path):
 
 _XLA_CALL = r"""
 import ctypes as C, sys
+sys.path.insert(0, sys.argv[3])
+import mpenv_abi
 fake = sys.argv[2]
 if fake:
     C.CDLL(fake, mode=C.RTLD_GLOBAL)
-lib = C.CDLL(sys.argv[1])
+lib = mpenv_abi.bind(C.CDLL(sys.argv[1]))
 Fn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t)
 FnS = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t, C.c_void_p)
 bad = bytes(24)
@@ -185,7 +226,6 @@ if fake:
     f = FnS(C.cast(lib.mpenv_xla_gpu_stream_step_status, C.c_void_p).value)
     status = C.create_string_buffer(8)
     f(None, None, bad, len(bad), C.cast(status, C.c_void_p))
-    lib.mpenv_xla_errors.restype = C.c_int64
     got = C.CDLL(fake).fake_status_message
     got.restype = C.c_char_p
     print("status:", got().decode(), "errors:", lib.mpenv_xla_errors())
@@ -203,8 +243,8 @@ def test_xla_v1_target_aborts_on_a_foreign_opaque():
     subprocess that never touches a GPU (the opaque check fails first)."""
     import sys
 
-    r = subprocess.run([sys.executable, "-c", _XLA_CALL, T.build_native.LIB, ""], capture_output=True, text=True,
-                       timeout=120)
+    r = subprocess.run([sys.executable, "-c", _XLA_CALL, T.build_native.LIB, "", HERE], capture_output=True,
+                       text=True, timeout=120)
     assert r.returncode != 0 and "returned" not in r.stdout
     assert "mpenv: XLA custom call gpuStreamStep failed: bad XLA opaque" in r.stderr, r.stderr
 
@@ -222,7 +262,7 @@ def test_xla_status_target_reports_failure_through_xla(tmp_path):
                    'const char *fake_status_message(void) { return msg; }\n')
     so = tmp_path / "libfake_xla.so"
     subprocess.run(["gcc", "-shared", "-fPIC", str(src), "-o", str(so)], check=True)
-    r = subprocess.run([sys.executable, "-c", _XLA_CALL, T.build_native.LIB, str(so)], capture_output=True,
+    r = subprocess.run([sys.executable, "-c", _XLA_CALL, T.build_native.LIB, str(so), HERE], capture_output=True,
                        text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert "status: mpenv: gpuStreamStep: bad XLA opaque" in r.stdout and "errors: 1" in r.stdout, r.stdout

@@ -13,21 +13,12 @@ which is what the exchanges add on top of the gloo-tested layout logic.
   and leaves the (one-rank) sum.
 """
 import os
-import socket
 
 import pytest
 
 import mpenv_testlib as T
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_learner_exchanges_on_rccl_one_rank():
@@ -38,7 +29,7 @@ def test_learner_exchanges_on_rccl_one_rank():
     from mpenv_dist import LearnerGather, make_exchange
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
+    os.environ["MASTER_PORT"] = str(T.free_port())
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:

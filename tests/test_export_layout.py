@@ -16,8 +16,6 @@ LOG_MODES = {"RECORD_LOG": (1, 0, 1), "EVENT_LOG": (1, 0, 1), "PACKED_STEP_SNAPS
 
 def engine_layout(export_id, num_worlds, team_size):
     lib = T.lib_mpenv()
-    lib.mpenv_export_layout.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     dt, nd = C.c_int32(-1), C.c_int32(-1)
     dims = (C.c_int64 * 8)()
     rc = lib.mpenv_export_layout(export_id, num_worlds, team_size, C.byref(dt), C.byref(nd), dims)

@@ -21,13 +21,6 @@ LIDAR_RAY, WORLD_RAY, SIGHT, CASTS, STUCK = range(5)
 SIZES = (1, 255, 257)  # around the hook's 256-thread block; the full set comes on top
 
 
-class GeomQueries(C.Structure):
-    _fields_ = [("o", C.c_void_p), ("d", C.c_void_p), ("caps", C.c_void_p), ("sel", C.c_void_p),
-                ("bound", C.c_void_p), ("z1", C.c_void_p), ("hint", C.c_void_p), ("t", C.c_void_p),
-                ("normal", C.c_void_p), ("i0", C.c_void_p), ("i1", C.c_void_p), ("num_caps", C.c_int32),
-                ("sub", C.c_int32)]
-
-
 class Hook:
     """Uploads a query set once; run() launches the hook on its first n
     queries and returns the outputs as numpy arrays."""
@@ -37,13 +30,11 @@ class Hook:
         self.torch = torch
         self.e = engine
         self.lib = T.lib_mpenv()
-        self.lib.mpenv_debug_geom_queries.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GeomQueries),
-                                                      C.c_void_p]
         self.dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in inputs.items()}
 
     def run(self, mode, n, outs, num_caps=0, sub=0, hint=None, t_init=None):
         torch = self.torch
-        q = GeomQueries()
+        q = T.GeomQueries()
         for k, v in self.dev.items():
             setattr(q, k, v.data_ptr())
         bufs = {}

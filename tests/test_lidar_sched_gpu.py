@@ -5,8 +5,6 @@ per batch or forced with mpenv_set_lidar_iters.  None of it may change an
 output byte: everything here is compared bit for bit, with the oracle or
 between runs.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -15,26 +13,6 @@ import mpenv_testlib as T
 pytestmark = pytest.mark.gpu
 
 LIDAR_EXPORTS = ["FWD_LIDAR", "REAR_LIDAR", "FULL_TEAM_FWD_LIDAR", "FULL_TEAM_REAR_LIDAR"]
-
-
-def set_iters(e, n):
-    e.lib.mpenv_set_lidar_iters.argtypes = [C.c_void_p, C.c_int32]
-    return e.lib.mpenv_set_lidar_iters(e.h, n)
-
-
-def captures(e):
-    e.lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    n = C.c_int64()
-    assert e.lib.mpenv_graph_captures(e.h, C.byref(n)) == 0
-    return n.value
-
-
-def graph_on(e):
-    e.lib.mpenv_graph_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int32]
-    on = C.c_int32()
-    why = C.create_string_buffer(512)
-    assert e.lib.mpenv_graph_status(e.h, C.byref(on), why, 512) == 0
-    return on.value != 0, why.value.decode()
 
 
 # (team size, worlds, forced iters); tasks = ceil(A / 4) * 5, 16 * iters per block
@@ -49,7 +27,7 @@ def test_lidar_sched_oracle_parity(ts, W, iters):
     A = W * 2 * ts
     e = T.Engine(W, ts)
     o = T.Oracle(W, ts)
-    assert set_iters(e, iters) == 0, e.lib.mpenv_last_error().decode()
+    assert e.set_lidar_iters(iters) == 0, e.lib.mpenv_last_error().decode()
     e.put_ctrl([0, 1, 1])
     o.put_ctrl([0, 1, 1])
     e.init()
@@ -84,7 +62,7 @@ def test_lidar_iters_do_not_change_a_byte():
     auto = T.Engine(W, ts)
     runs = {n: T.Engine(W, ts) for n in forced}
     for n, e in runs.items():
-        assert set_iters(e, n) == 0, e.lib.mpenv_last_error().decode()
+        assert e.set_lidar_iters(n) == 0, e.lib.mpenv_last_error().decode()
     for e in [auto] + list(runs.values()):
         e.put_ctrl([0, 1, 1])
         e.init()
@@ -106,15 +84,15 @@ def test_lidar_iters_do_not_change_a_byte():
         check(s, runs)
     # one engine, the value changed between steps
     ref = {12: runs[12]}
-    c0 = captures(auto)
-    assert c0 >= 1 and graph_on(auto)[0], graph_on(auto)
+    c0 = auto.graph_captures()
+    assert c0 >= 1 and auto.graph_status()[0], auto.graph_status()
     for k, n in enumerate((1, 2, 6, 12, 0)):
-        assert set_iters(auto, n) == 0, auto.lib.mpenv_last_error().decode()
+        assert auto.set_lidar_iters(n) == 0, auto.lib.mpenv_last_error().decode()
         for rep in range(2):  # the second step with the same value replays the graph
             step_all(steps + 2 * k + rep, [auto, runs[12]])
-            assert captures(auto) == c0 + k + 1, (n, rep, captures(auto), c0)
+            assert auto.graph_captures() == c0 + k + 1, (n, rep, auto.graph_captures(), c0)
         check(steps + 2 * k + 1, ref)
-    assert graph_on(auto) == (True, ""), graph_on(auto)
+    assert auto.graph_status() == (True, ""), auto.graph_status()
     for e in [auto] + list(runs.values()):
         e.close()
 
@@ -122,9 +100,9 @@ def test_lidar_iters_do_not_change_a_byte():
 def test_lidar_iters_out_of_range():
     e = T.Engine(4, 2)
     for n in (-1, 13, 1 << 20):
-        assert set_iters(e, n) != 0
+        assert e.set_lidar_iters(n) != 0
         assert "lidar iters" in e.lib.mpenv_last_error().decode()
-    assert set_iters(e, 12) == 0 and set_iters(e, 0) == 0
+    assert e.set_lidar_iters(12) == 0 and e.set_lidar_iters(0) == 0
     e.close()
 
     import madrona_mp_env as m
@@ -147,52 +125,31 @@ def test_lidar_sched_stream_path():
 
     ts, W, iters = 3, 5, 2
     A = W * 2 * ts
-    lib = T.lib_mpenv()
-    lib.mpenv_gpu_stream_init.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_gpu_stream_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_train_interface_entry.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
-                                                C.POINTER(C.c_int32)]
     e = T.Engine(W, ts)
     o = T.Oracle(W, ts)
-    assert set_iters(e, iters) == 0, lib.mpenv_last_error().decode()
-    ni, no = C.c_int32(), C.c_int32()
-    assert lib.mpenv_train_interface_size(C.byref(ni), C.byref(no)) == 0
-    names, sets = [], [[], []]
-    inv = {v: k for k, v in T.EXPORT.items()}
-    for io, n in ((0, ni.value), (1, no.value)):
-        for k in range(n):
-            nm, eid = C.c_char_p(), C.c_int32()
-            assert lib.mpenv_train_interface_entry(io, k, C.byref(nm), C.byref(eid)) == 0
-            _, dt, shape = e.desc(inv[eid.value])
-            tdt = {np.int32: torch.int32, np.float32: torch.float32}[dt]
-            names.append((io, nm.value.decode(), inv[eid.value]))
-            for bs in sets:
-                bs.append(torch.full(shape, 7 if io == 1 else 0, dtype=tdt, device="cuda"))
-    arrs = [(C.c_void_p * len(bs))(*[b.data_ptr() for b in bs]) for bs in sets]
-    idx = {nm: i for i, (io, nm, _) in enumerate(names)}
+    assert e.set_lidar_iters(iters) == 0, e.lib.mpenv_last_error().decode()
+    sb = T.StreamBuffers(e)
+    sets, arrs, idx = sb.sets, sb.arrs, sb.idx
     maps = ("agent_map", "unmasked_agent_map")
     nan_filled = ("fwd_lidar", "rear_lidar") + maps
-    for bs in sets:
-        bs[idx["simCtrl"]].copy_(torch.tensor([0, 1, 1], dtype=torch.int32).view_as(bs[idx["simCtrl"]]))
     o.put_ctrl([0, 1, 1])
     e.put_ctrl([0, 1, 1])
     stream = torch.cuda.Stream()
-    assert lib.mpenv_gpu_stream_init(e.h, C.c_void_p(stream.cuda_stream), arrs[0]) == 0
+    e.gpu_stream_init(stream.cuda_stream, arrs[0])
     o.init()
     stream.synchronize()
     for s in range(6):
         bufs = sets[s % 2]
         acts = T.mpenv_tape.tape_actions(1234, s, 0, A)
-        bufs[idx["discrete"]].copy_(torch.from_numpy(acts[:, :4].copy()).view_as(bufs[idx["discrete"]]))
-        bufs[idx["aim"]].copy_(torch.from_numpy(acts[:, 4:6].copy()).view_as(bufs[idx["aim"]]))
+        sb.set_actions(s % 2, acts)
         for nm in nan_filled:
             bufs[idx[nm]].fill_(float("nan"))
         torch.cuda.synchronize()
-        assert lib.mpenv_gpu_stream_step(e.h, C.c_void_p(stream.cuda_stream), arrs[s % 2]) == 0
+        e.gpu_stream_step(stream.cuda_stream, arrs[s % 2])
         o.set_actions(acts)
         o.step()
         stream.synchronize()
-        for (io, nm, ename), b in zip(names, bufs):
+        for (io, nm, ename, _, _), b in zip(sb.ti, bufs):
             if io != 1:
                 continue
             got = b.cpu().numpy()
@@ -208,7 +165,7 @@ def test_lidar_sched_stream_path():
     e.step()
     o.set_actions(acts)
     o.step()
-    for (io, nm, ename) in names:
+    for (io, nm, ename, _, _) in sb.ti:
         if io == 1 and nm not in maps:
             T.compare(e.get(ename), o.get(ename), f"engine export {ename} after the stream steps")
     for name in LIDAR_EXPORTS:

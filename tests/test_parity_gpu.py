@@ -492,62 +492,36 @@ def test_gpu_stream_step_buffers_abi(groups):
     output of the set a step used equals the oracle, and the captured step
     graph is not re-captured for them.  Afterwards a plain step() writes the
     engine's own exports again (the table is off outside the call)."""
-    import ctypes as C
     import torch
 
     ts, W = 2, 16
     A = W * 2 * ts
-    lib = T.lib_mpenv()
-    lib.mpenv_gpu_stream_init.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_gpu_stream_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_train_interface_entry.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_char_p),
-                                                C.POINTER(C.c_int32)]
     e = T.Engine(W, ts)
     o = T.Oracle(W, ts)
-    ni, no = C.c_int32(), C.c_int32()
-    assert lib.mpenv_train_interface_size(C.byref(ni), C.byref(no)) == 0
     if groups > 1:
-        lib.mpenv_set_world_groups.argtypes = [C.c_void_p, C.c_int32]
-        assert lib.mpenv_set_world_groups(e.h, groups) == 0
-    names, sets = [], [[], []]
-    inv = {v: k for k, v in T.EXPORT.items()}
-    for io, n in ((0, ni.value), (1, no.value)):
-        for k in range(n):
-            nm, eid = C.c_char_p(), C.c_int32()
-            assert lib.mpenv_train_interface_entry(io, k, C.byref(nm), C.byref(eid)) == 0
-            _, dt, shape = e.desc(inv[eid.value])
-            tdt = {np.int32: torch.int32, np.float32: torch.float32}[dt]
-            names.append((io, nm.value.decode(), inv[eid.value]))
-            for bs in sets:  # outputs not zeros: every byte must be written
-                bs.append(torch.full(shape, 7 if io == 1 else 0, dtype=tdt, device="cuda"))
-    arrs = [(C.c_void_p * len(bs))(*[b.data_ptr() for b in bs]) for bs in sets]
-    idx = {nm: i for i, (io, nm, _) in enumerate(names)}
-    for bs in sets:
-        bs[idx["simCtrl"]].copy_(torch.tensor([0, 1, 1], dtype=torch.int32).view_as(bs[idx["simCtrl"]]))
+        e.set_world_groups(groups)
+    sb = T.StreamBuffers(e)  # outputs not zeros: every byte must be written
+    sets, arrs = sb.sets, sb.arrs
     o.put_ctrl([0, 1, 1])
     stream = torch.cuda.Stream()
     e.put_ctrl([0, 1, 1])
-    assert lib.mpenv_gpu_stream_init(e.h, C.c_void_p(stream.cuda_stream), arrs[0]) == 0
+    e.gpu_stream_init(stream.cuda_stream, arrs[0])
     o.init()
     stream.synchronize()
-    lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     caps = []
     for s in range(40):
         bufs = sets[s % 2]
         acts = T.mpenv_tape.tape_actions(1234, s, 0, A)
-        bufs[idx["discrete"]].copy_(torch.from_numpy(acts[:, :4].copy()).view_as(bufs[idx["discrete"]]))
-        bufs[idx["aim"]].copy_(torch.from_numpy(acts[:, 4:6].copy()).view_as(bufs[idx["aim"]]))
+        sb.set_actions(s % 2, acts)
         torch.cuda.synchronize()
-        assert lib.mpenv_gpu_stream_step(e.h, C.c_void_p(stream.cuda_stream), arrs[s % 2]) == 0
+        e.gpu_stream_step(stream.cuda_stream, arrs[s % 2])
         o.set_actions(acts)
         o.step()
         stream.synchronize()
-        for (io, nm, ename), b in zip(names, bufs):
+        for (io, nm, ename, _, _), b in zip(sb.ti, bufs):
             if io == 1:
                 T.compare(b.cpu().numpy(), o.get(ename), f"{nm} @ {s}")
-        n = C.c_int64()
-        assert lib.mpenv_graph_captures(e.h, C.byref(n)) == 0
-        caps.append(n.value)
+        caps.append(e.graph_captures())
     assert caps[1] >= 1 and caps[-1] == caps[1], caps  # one capture serves both buffer sets
     # a plain step afterwards: the engine's own exports are written again
     acts = T.mpenv_tape.tape_actions(1234, 40, 0, A)
@@ -555,7 +529,7 @@ def test_gpu_stream_step_buffers_abi(groups):
     e.step()
     o.set_actions(acts)
     o.step()
-    for (io, nm, ename) in names:
+    for (io, nm, ename, _, _) in sb.ti:
         if io == 1 and nm != "unmasked_agent_map" and nm != "agent_map":
             T.compare(e.get(ename), o.get(ename), f"engine export {nm} after the stream steps")
 
@@ -612,7 +586,6 @@ def test_jax_custom_call_targets_match_gpu_stream_step():
     with pytest.raises(ValueError):
         b.gpu_stream_step(0, ptrs_b[:-1])
     lib = T.lib_mpenv()
-    lib.mpenv_xla_errors.restype = C.c_int64
     errs0 = lib.mpenv_xla_errors()
     stream = torch.cuda.Stream()
     # the reference's ordering: gpuStreamInit's forced reset reads simCtrl
@@ -654,8 +627,6 @@ def test_bvh_traversal_matches_oracle_on_edge_cases():
     import torch
 
     lib = T.lib_mpenv()
-    lib.mpenv_debug_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
     e = T.Engine(1, 1)
     o = T.Oracle(1, 1)
     nodes, verts, _ = T.scene_bvh()
@@ -742,7 +713,6 @@ def test_step_graph_captures_every_fork_layout(monkeypatch):
     for groups, branch in layouts:
         e = T.Engine(W, ts)
         e.set_world_groups(groups)
-        e.lib.mpenv_set_lidar_branch.argtypes = [C.c_void_p, C.c_int32]
         assert e.lib.mpenv_set_lidar_branch(e.h, int(branch)) == 0
         engines.append(e)
     for e in [ref] + engines:
@@ -758,13 +728,10 @@ def test_step_graph_captures_every_fork_layout(monkeypatch):
                 for n in T.STEP_OUTPUTS:
                     T.compare(e.get(n), ref.get(n), f"{n} graph ({groups} groups, branch {branch}) vs direct @ {s}")
     for (groups, branch), e in zip(layouts, engines):
-        on, why = C.c_int32(-1), C.create_string_buffer(512)
-        e.lib.mpenv_graph_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int32]
-        assert e.lib.mpenv_graph_status(e.h, C.byref(on), why, 512) == 0
-        assert on.value == 1 and why.value == b"", (groups, branch, why.value)
-        n_cap = C.c_int64(-1)
-        e.lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        assert e.lib.mpenv_graph_captures(e.h, C.byref(n_cap)) == 0 and n_cap.value == 1, (groups, branch, n_cap.value)
+        on, why = e.graph_status()
+        assert on == 1 and why == "", (groups, branch, why)
+        n_cap = e.graph_captures()
+        assert n_cap == 1, (groups, branch, n_cap)
         e.close()
     ref.close()
 
@@ -824,14 +791,10 @@ def test_step_graph_replay_equals_direct_launches(monkeypatch):
     # one capture per argument change and none otherwise: steps 0 (first),
     # 8 (3 groups), 16 (stats on), 20 (stats off + 1 group), 28 (2 groups);
     # the timed steps 34-37 bypass the graph and 38 replays the step-28 graph
-    import ctypes as C
-    n_cap = C.c_int64(-1)
-    g.lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    assert g.lib.mpenv_graph_captures(g.h, C.byref(n_cap)) == 0
-    assert n_cap.value == 5, n_cap.value
+    n_cap = g.graph_captures()
+    assert n_cap == 5, n_cap
     # a re-capture right after an asynchronous launch (the previous exec may
     # still run): groups 2 -> 3 with no sync between, then both engines agree
-    g.lib.mpenv_step_async.argtypes = [C.c_void_p, C.c_void_p]
     acts = T.mpenv_tape.tape_actions(1234, steps, 0, W * N)
     for e in (ref, g):
         e.set_actions(acts)

@@ -33,15 +33,6 @@ def ckpt(tmp_path_factory):
     return str(d), P.Ref(tensors)
 
 
-def lib():
-    l = P.policy_lib()
-    l.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    l.mpenv_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    l.mpenv_state_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    l.mpenv_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return l
-
-
 def engine(ts, W, groups=1, **kw):
     e = T.Engine(W, ts, **kw)
     if groups > 1:
@@ -52,19 +43,13 @@ def engine(ts, W, groups=1, **kw):
 
 
 def load(e, d):
-    assert lib().mpenv_policy_load(e.h, d.encode()) == 0, e.lib.mpenv_last_error().decode()
+    assert e.lib.mpenv_policy_load(e.h, d.encode()) == 0, e.lib.mpenv_last_error().decode()
 
 
 def loaded(e):
     on = C.c_int32(-1)
-    assert lib().mpenv_policy_loaded(e.h, C.byref(on)) == 0
+    assert e.lib.mpenv_policy_loaded(e.h, C.byref(on)) == 0
     return on.value
-
-
-def captures(e):
-    n = C.c_int64()
-    assert lib().mpenv_graph_captures(e.h, C.byref(n)) == 0
-    return n.value
 
 
 def outputs(e):
@@ -124,7 +109,7 @@ def test_dense_equals_the_cpu_chain_bit_for_bit(K):
             want = P.ref_dense(x, w)
             xd = e.mem.upload(x)
             yd = e.mem.upload(np.full((M, N), np.nan, np.float32))
-            rc = lib().mpenv_debug_policy_dense(e.h, xd, M, K, w.ctypes.data, N, yd, None)
+            rc = e.lib.mpenv_debug_policy_dense(e.h, xd, M, K, w.ctypes.data, N, yd, None)
             assert rc == 0, e.lib.mpenv_last_error().decode()
             got = np.empty((M, N), np.float32)
             e.mem.d2h(yd, got.nbytes, got)
@@ -156,7 +141,7 @@ def test_forward_equals_the_restatement_and_writes_no_state(ckpt, ts, W, groups)
     assert (before["OPPONENT_MASKS"] > 0).any() or ts == 1
     lg_d = e.mem.upload(np.full((A, P.LOGITS), np.nan, np.float32))
     ac_d = e.mem.upload(np.full((A, 6), -7, np.int32))
-    assert lib().mpenv_policy_forward(e.h, lg_d, ac_d, None) == 0, e.lib.mpenv_last_error().decode()
+    assert e.lib.mpenv_policy_forward(e.h, lg_d, ac_d, None) == 0, e.lib.mpenv_last_error().decode()
     e.mem.hip.hipDeviceSynchronize()
     logits, acts = np.empty((A, P.LOGITS), np.float32), np.empty((A, 6), np.int32)
     e.mem.d2h(lg_d, logits.nbytes, logits)
@@ -168,7 +153,7 @@ def test_forward_equals_the_restatement_and_writes_no_state(ckpt, ts, W, groups)
     T.compare(acts, want_acts, "actions")
     # logits only: the actions buffer stays as it was
     e.mem.h2d(ac_d, np.full((A, 6), -7, np.int32))
-    assert lib().mpenv_policy_forward(e.h, lg_d, None, None) == 0
+    assert e.lib.mpenv_policy_forward(e.h, lg_d, None, None) == 0
     e.mem.hip.hipDeviceSynchronize()
     e.mem.d2h(ac_d, acts.nbytes, acts)
     assert (acts == -7).all()
@@ -200,9 +185,7 @@ def test_step_writes_policy_agents_actions_and_twin_trajectory_matches(ckpt, ts,
         e.put("AGENT_POLICY", ids)
     load(a, d)
     assert loaded(a) == 1 and loaded(b) == 0
-    nb = C.c_int64()
-    assert lib().mpenv_state_bytes(b.h, C.byref(nb)) == 0
-    blob = torch.empty(nb.value, dtype=torch.uint8, device="cuda")
+    blob = torch.empty(b.state_bytes(), dtype=torch.uint8, device="cuda")
     pol_t = torch.from_numpy(np.flatnonzero(pol)).cuda()
     caps = []
     for s in range(30):
@@ -213,15 +196,15 @@ def test_step_writes_policy_agents_actions_and_twin_trajectory_matches(ckpt, ts,
             obs = {k: v[pol] for k, v in P.engine_obs(a).items()}
             want, _ = ref.sample(ref.forward(obs), *(r[pol] for r in rng_of(a)))
         a.step()
-        caps.append(captures(a))
+        caps.append(a.graph_captures())
         played = actions_of(a)
         if check:
             T.compare(played[pol], want, f"policy agents' actions @ {s}")
         T.compare(played[alone], given[alone], f"actions of agents with policy -2 @ {s}")
         # B: the same step without a policy
-        assert lib().mpenv_state_save(b.h, blob.data_ptr(), None) == 0
+        b.state_save(blob.data_ptr())
         mpenv_state.view(blob, "rngCtr")[pol_t] += 6
-        assert lib().mpenv_state_load(b.h, blob.data_ptr(), None, None) == 0
+        b.state_load(blob.data_ptr())
         b.set_actions(played)
         b.step()
         compare_all(outputs(a), outputs(b), f"step {s}")
@@ -237,35 +220,18 @@ def test_gpu_stream_step_plays_the_same_actions_as_step(ckpt):
 
     d, _ = ckpt
     ts, W = 3, 7
-    l = lib()
-    l.mpenv_gpu_stream_init.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    l.mpenv_gpu_stream_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    l.mpenv_train_interface_entry.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     a = engine(ts, W)
     b = T.Engine(W, ts)
     A = a.W * a.N
     ids = mixed_ids(A)
-    ni, no = C.c_int32(), C.c_int32()
-    assert l.mpenv_train_interface_size(C.byref(ni), C.byref(no)) == 0
-    inv = {v: k for k, v in T.EXPORT.items()}
-    names, bufs = [], []
-    for io, n in ((0, ni.value), (1, no.value)):
-        for k in range(n):
-            nm, eid = C.c_char_p(), C.c_int32()
-            assert l.mpenv_train_interface_entry(io, k, C.byref(nm), C.byref(eid)) == 0
-            _, dt, shape = b.desc(inv[eid.value])
-            names.append((io, nm.value.decode(), inv[eid.value]))
-            bufs.append(torch.full(shape, 7 if io == 1 else 0, device="cuda",
-                                   dtype={np.int32: torch.int32, np.float32: torch.float32}[dt]))
-    arr = (C.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
-    idx = {nm: i for i, (_io, nm, _e) in enumerate(names)}
-    bufs[idx["simCtrl"]].copy_(torch.tensor([0, 1, 1], dtype=torch.int32).view_as(bufs[idx["simCtrl"]]))
-    bufs[idx["pbt.policy_assignments"]].copy_(torch.from_numpy(ids).view_as(bufs[idx["pbt.policy_assignments"]]))
+    sb = T.StreamBuffers(b, n_sets=1)
+    bufs, arr = sb.sets[0], sb.arrs[0]
+    sb.put(0, "pbt.policy_assignments", ids)
     a.put("AGENT_POLICY", ids)
     b.put_ctrl([0, 1, 1])
     stream = torch.cuda.Stream()
     torch.cuda.synchronize()
-    assert l.mpenv_gpu_stream_init(b.h, C.c_void_p(stream.cuda_stream), arr) == 0
+    b.gpu_stream_init(stream.cuda_stream, arr)
     stream.synchronize()
     load(a, d)
     load(b, d)
@@ -273,13 +239,12 @@ def test_gpu_stream_step_plays_the_same_actions_as_step(ckpt):
         given = T.mpenv_tape.tape_actions(SEED, s, 0, A)
         a.set_actions(given)
         a.step()
-        bufs[idx["discrete"]].copy_(torch.from_numpy(given[:, :4].copy()).view_as(bufs[idx["discrete"]]))
-        bufs[idx["aim"]].copy_(torch.from_numpy(given[:, 4:6].copy()).view_as(bufs[idx["aim"]]))
+        sb.set_actions(0, given)
         torch.cuda.synchronize()
-        assert l.mpenv_gpu_stream_step(b.h, C.c_void_p(stream.cuda_stream), arr) == 0
+        b.gpu_stream_step(stream.cuda_stream, arr)
         stream.synchronize()
         T.compare(actions_of(b), actions_of(a), f"played actions @ {s}")
-        for (io, nm, ename), t in zip(names, bufs):
+        for (io, nm, ename, _, _), t in zip(sb.ti, bufs):
             if io == 1 and "agent_map" not in nm:
                 T.compare(t.cpu().numpy(), a.get(ename), f"{nm} @ {s}")
     compare_all(outputs(b), outputs(a), "after the stream steps")
@@ -298,7 +263,7 @@ def test_unloaded_manager_equals_one_that_never_loaded(ckpt):
     for s in range(6):
         if s == 3:
             assert loaded(a) == 1
-            assert lib().mpenv_policy_unload(a.h) == 0
+            assert a.lib.mpenv_policy_unload(a.h) == 0
             assert loaded(a) == 0
             for e in (a, b):  # everybody on it: nothing is loaded to evaluate
                 e.put("AGENT_POLICY", np.zeros(A, np.int32))
@@ -308,7 +273,7 @@ def test_unloaded_manager_equals_one_that_never_loaded(ckpt):
             e.step()
         compare_all(outputs(a), outputs(b), f"step {s}")
     lg = a.mem.upload(np.zeros((A, P.LOGITS), np.float32))
-    assert lib().mpenv_policy_forward(a.h, lg, None, None) == ERR_INVALID
+    assert a.lib.mpenv_policy_forward(a.h, lg, None, None) == ERR_INVALID
     assert "no policy loaded" in a.lib.mpenv_last_error().decode()
     a.mem.free(lg)
     a.close()
@@ -320,30 +285,30 @@ def test_unloaded_manager_equals_one_that_never_loaded(ckpt):
 def test_refusals_name_their_reason(ckpt, tmp_path):
     d, _ = ckpt
     rec = T.Engine(2, 1, record=str(tmp_path / "rec.bin"))
-    assert lib().mpenv_policy_load(rec.h, d.encode()) == ERR_INVALID
+    assert rec.lib.mpenv_policy_load(rec.h, d.encode()) == ERR_INVALID
     assert "record_log_path" in rec.lib.mpenv_last_error().decode()
     rec.put_ctrl([0, 1, 1])
     rec.init()
     rec.step()
     rec.close()
     rep = T.Engine(2, 1, replay=str(tmp_path / "rec.bin"))
-    assert lib().mpenv_policy_load(rep.h, d.encode()) == ERR_INVALID
+    assert rep.lib.mpenv_policy_load(rep.h, d.encode()) == ERR_INVALID
     assert "replay_log_path" in rep.lib.mpenv_last_error().decode()
     rep.close()
     (tmp_path / "events").mkdir()
     ev = T.Engine(2, 1, events=str(tmp_path / "events"))
-    assert lib().mpenv_policy_load(ev.h, d.encode()) == ERR_INVALID
+    assert ev.lib.mpenv_policy_load(ev.h, d.encode()) == ERR_INVALID
     assert "event_log_path" in ev.lib.mpenv_last_error().decode()
     ev.close()
     ft = T.Engine(2, 1, sim_flags=FULL_TEAM_POLICY)
-    assert lib().mpenv_policy_load(ft.h, d.encode()) == ERR_INVALID
+    assert ft.lib.mpenv_policy_load(ft.h, d.encode()) == ERR_INVALID
     assert "FullTeamPolicy" in ft.lib.mpenv_last_error().decode()
     ft.close()
     e = T.Engine(2, 1)
     broken = tmp_path / "broken"
     P.write_checkpoint(broken, 1)
     os.remove(broken / "params_backbone_prefix_self_embed_kernel")
-    assert lib().mpenv_policy_load(e.h, str(broken).encode()) == -2
+    assert e.lib.mpenv_policy_load(e.h, str(broken).encode()) == -2
     assert "params_backbone_prefix_self_embed_kernel" in e.lib.mpenv_last_error().decode()
     assert loaded(e) == 0
     e.close()

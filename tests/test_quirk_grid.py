@@ -18,7 +18,6 @@ R = 15.0  # consts::agentRadius, the only sphere-cast radius
 
 def quirk_grid(scene=T.SCENE):
     lib = T.lib_mpenv()
-    lib.mpenv_scene_quirk_grid.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     n = C.c_int32(0)
     hdr = np.zeros(5, dtype=np.int32)
     assert lib.mpenv_scene_quirk_grid(scene.encode(), hdr.ctypes.data, None, C.byref(n)) == 0

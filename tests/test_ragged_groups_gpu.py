@@ -14,8 +14,6 @@ is the aligned control.
 
 Shapes are (team size, worlds, world groups); groups split at W * i / groups
 (mpenv_manager::setupGroups)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -51,13 +49,6 @@ def misaligned_spans(ts, W, groups):
     """{n: some group's first agent g0 has g0 * n * 4 % 16 != 0}"""
     N = 2 * ts
     return {n: any((w0 * N * n * 4) % 16 != 0 for w0 in group_starts(W, groups)) for n in SPAN_FLOATS}
-
-
-def captures(e):
-    n = C.c_int64(-1)
-    e.lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    assert e.lib.mpenv_graph_captures(e.h, C.byref(n)) == 0
-    return n.value
 
 
 def lidar_classes(o):
@@ -115,7 +106,8 @@ def test_misaligned_world_groups_match_the_oracle(monkeypatch, ts, W, groups):
     # what the run reached, from the oracle alone
     assert classes == ({0, 1, 3} if ts == 1 else {0, 1, 2, 3}), classes
     assert masks and lk_obs and lk_pos
-    assert captures(direct) == 0 and captures(graph) == 1, (captures(direct), captures(graph))
+    caps = direct.graph_captures(), graph.graph_captures()
+    assert caps == (0, 1), caps
     for e in engines.values():
         e.close()
     o.close()

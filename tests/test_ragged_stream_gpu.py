@@ -12,8 +12,6 @@ into its allocation (directTable must fall back to copying, copyTI to
 hipMemcpyAsync for that buffer); and a null output pointer (skipped).
 
 Shapes are (team size, worlds, world groups)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -31,32 +29,6 @@ DIRECT = {"fwd_lidar", "rear_lidar", "self", "filters_state", "teammates", "oppo
           "teammate_positions", "opponent_positions", "opponent_masks", "agent_map", "unmasked_agent_map"}
 
 
-def _lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_gpu_stream_init.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_gpu_stream_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.mpenv_train_interface_size.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.mpenv_train_interface_entry.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
-    lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    return lib
-
-
-def interface(e):
-    """[(is_output, name, export name, numpy dtype, shape)] in buffer order"""
-    lib = _lib()
-    ni, no = C.c_int32(), C.c_int32()
-    assert lib.mpenv_train_interface_size(C.byref(ni), C.byref(no)) == 0
-    inv = {v: k for k, v in T.EXPORT.items()}
-    out = []
-    for io, n in ((0, ni.value), (1, no.value)):
-        for k in range(n):
-            nm, eid = C.c_char_p(), C.c_int32()
-            assert lib.mpenv_train_interface_entry(io, k, C.byref(nm), C.byref(eid)) == 0
-            _, dt, shape = e.desc(inv[eid.value])
-            out.append((io, nm.value.decode(), inv[eid.value], dt, shape))
-    return out
-
-
 def run(ts, W, groups, offset_output=None, null_output=None):
     """The structure of test_gpu_stream_step_buffers_abi: two caller buffer
     sets alternate, outputs pre-filled with 7, every output of the set a step
@@ -68,13 +40,13 @@ def run(ts, W, groups, offset_output=None, null_output=None):
     buffer must keep its 7s."""
     import torch
 
-    lib = _lib()
     A = W * 2 * ts
     e = T.Engine(W, ts)
     o = T.Oracle(W, ts)
     if groups > 1:
         e.set_world_groups(groups)
-    ti = interface(e)
+    sb = T.StreamBuffers(e)
+    ti, sets, idx = sb.ti, sb.sets, sb.idx
     names = [nm for _, nm, _, _, _ in ti]
     assert DIRECT <= set(names) and offset_output in DIRECT | {None} and null_output not in DIRECT
     # what the copies are made of, from the export descriptors: a segment with
@@ -85,32 +57,22 @@ def run(ts, W, groups, offset_output=None, null_output=None):
     if groups > 1:  # some group's first agent is off the 4-agent boundary
         assert any((W * i // groups * 2 * ts) % 4 for i in range(1, groups))
 
-    sets = [[], []]
-    for io, nm, _, dt, shape in ti:
-        tdt = {np.int32: torch.int32, np.float32: torch.float32}[dt]
-        n = int(np.prod(shape))
-        for bs in sets:  # outputs not zeros: every byte must be written
-            if nm == offset_output:
-                whole = torch.full((n + 4,), 7, dtype=tdt, device="cuda")
-                t = whole[1:n + 1].view(shape)
-                assert t.data_ptr() % 16 == 4
-            else:
-                t = torch.full(shape, 7 if io == 1 else 0, dtype=tdt, device="cuda")
-                assert t.data_ptr() % 16 == 0
-            bs.append(t)
-    idx = {nm: i for i, nm in enumerate(names)}
-    arrs = []
     for bs in sets:
-        ptrs = [b.data_ptr() for b in bs]
-        if null_output:
-            ptrs[idx[null_output]] = None
-        arrs.append((C.c_void_p * len(ptrs))(*ptrs))
-    for bs in sets:
-        bs[idx["simCtrl"]].copy_(torch.tensor([0, 1, 1], dtype=torch.int32).view_as(bs[idx["simCtrl"]]))
+        assert all(t.data_ptr() % 16 == 0 for t in bs)
+        if offset_output:
+            t = bs[idx[offset_output]]
+            whole = torch.full((t.numel() + 4,), 7, dtype=t.dtype, device="cuda")
+            bs[idx[offset_output]] = whole[1:t.numel() + 1].view(t.shape)
+            assert bs[idx[offset_output]].data_ptr() % 16 == 4
+    sb.point()
+    arrs = sb.arrs
+    if null_output:
+        for arr in arrs:
+            arr[idx[null_output]] = None
     o.put_ctrl([0, 1, 1])
     e.put_ctrl([0, 1, 1])
     stream = torch.cuda.Stream()
-    assert lib.mpenv_gpu_stream_init(e.h, C.c_void_p(stream.cuda_stream), arrs[0]) == 0
+    e.gpu_stream_init(stream.cuda_stream, arrs[0])
     o.init()
     stream.synchronize()
 
@@ -129,18 +91,14 @@ def run(ts, W, groups, offset_output=None, null_output=None):
     for s in range(STEPS):
         bufs = sets[s % 2]
         acts = T.mpenv_tape.tape_actions(SEED, s, 0, A)
-        bufs[idx["discrete"]].copy_(torch.from_numpy(acts[:, :4].copy()).view_as(bufs[idx["discrete"]]))
-        bufs[idx["aim"]].copy_(torch.from_numpy(acts[:, 4:6].copy()).view_as(bufs[idx["aim"]]))
+        sb.set_actions(s % 2, acts)
         torch.cuda.synchronize()
-        assert lib.mpenv_gpu_stream_step(e.h, C.c_void_p(stream.cuda_stream), arrs[s % 2]) == 0, \
-            lib.mpenv_last_error().decode()
+        e.gpu_stream_step(stream.cuda_stream, arrs[s % 2])
         o.set_actions(acts)
         o.step()
         stream.synchronize()
         check(bufs, f"step {s}")
-        n = C.c_int64()
-        assert lib.mpenv_graph_captures(e.h, C.byref(n)) == 0
-        caps.append(n.value)
+        caps.append(e.graph_captures())
     assert caps[0] >= 1 and caps[-1] == caps[0], caps  # one capture serves both buffer sets
     if offset_output:  # the guard elements around the offset view are untouched
         for bs in sets:

@@ -304,8 +304,6 @@ def test_node_bytes_follow_the_documented_quantisation(bvh):
 def _variant(scene, opts):
     lib = T.lib_mpenv()
     fn = lib.mpenv_scene_bvh_variant
-    fn.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p,
-                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     o = np.asarray(opts, np.int32)
     nn, nv, ms = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     assert fn(scene.encode(), o.ctypes.data, len(o), None, C.byref(nn), None, C.byref(nv), C.byref(ms)) == 0

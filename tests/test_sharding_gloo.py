@@ -8,7 +8,6 @@ here (no GPU on CPU runners); the GPU tests check the engine with the same
 world_id_offset mechanism.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -21,14 +20,6 @@ from mpenv_dist import LearnerGather, shard_worlds, gather_to_learner
 
 TOTAL_WORLDS, TEAM, STEPS = 6, 2, 60
 OUTS = ["SELF_OBSERVATION", "FWD_LIDAR", "REWARD", "DONE", "HP", "MATCH_RESULT"]
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _run(sim, first_agent, n_agents):
@@ -71,7 +62,7 @@ def test_shard_worlds_partition():
 
 def test_two_rank_shards_equal_single_run(tmp_path):
     path = str(tmp_path / "gathered.npz")
-    mp.spawn(_worker, args=(2, _free_port(), path), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, T.free_port(), path), nprocs=2, join=True)
     got = np.load(path)
     full = _run(T.Oracle(TOTAL_WORLDS, TEAM), 0, TOTAL_WORLDS * 2 * TEAM)
     for k, name in enumerate(OUTS):
@@ -118,7 +109,7 @@ def test_learner_gather_ships_every_train_output_in_global_order(tmp_path):
     the two ring slots hold the last two steps, and flattening the rank axis
     gives the single-run tensors in global world order."""
     path = str(tmp_path / "lg.npz")
-    mp.spawn(_lg_worker, args=(2, _free_port(), path), nprocs=2, join=True)
+    mp.spawn(_lg_worker, args=(2, T.free_port(), path), nprocs=2, join=True)
     got = np.load(path)
     o = T.Oracle(TOTAL_WORLDS, TEAM)
     o.put_ctrl([0, 1, 1])
@@ -168,7 +159,7 @@ def test_learner_local_exchange_keeps_shards_and_allreduces_gradients(tmp_path):
     run's rows of those worlds), and every `update_every` steps one
     all-reduce of the gradient-sized buffer runs (sum over ranks)."""
     path = str(tmp_path / "loc")
-    mp.spawn(_local_worker, args=(2, _free_port(), path), nprocs=2, join=True)
+    mp.spawn(_local_worker, args=(2, T.free_port(), path), nprocs=2, join=True)
     o = T.Oracle(TOTAL_WORLDS, TEAM)
     o.put_ctrl([0, 1, 1])
     o.init()
@@ -211,7 +202,7 @@ def test_learner_gather_rejects_unequal_shards(tmp_path):
     """An uneven split (5 worlds on 2 ranks) would make RCCL's gather truncate
     or overrun silently: LearnerGather checks every rank's layout up front."""
     path = str(tmp_path / "uneven")
-    mp.spawn(_uneven_worker, args=(2, _free_port(), path), nprocs=2, join=True)
+    mp.spawn(_uneven_worker, args=(2, T.free_port(), path), nprocs=2, join=True)
     for rank in range(2):
         assert "different layout" in open(path + f".{rank}").read()
 
@@ -288,7 +279,7 @@ def test_learner_wire_transport_three_ranks(tmp_path, dedicated):
     import pickle  # reads the file _wire_worker wrote above
 
     path = str(tmp_path / "wire.pkl")
-    mp.spawn(_wire_worker, args=(3, _free_port(), path, dedicated), nprocs=3, join=True)
+    mp.spawn(_wire_worker, args=(3, T.free_port(), path, dedicated), nprocs=3, join=True)
     with open(path, "rb") as f:
         seen = pickle.load(f)
     for r in (1, 2):
@@ -308,7 +299,7 @@ def test_learner_wire_check_raises_when_a_shadow_refused_a_message():
     from mpenv_dist import LearnerWire
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
+    os.environ["MASTER_PORT"] = str(T.free_port())
     dist.init_process_group("gloo", rank=0, world_size=1)
     try:
         err = {0: 0}

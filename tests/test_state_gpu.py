@@ -8,7 +8,6 @@ shapes are the smallest at which the copies can go wrong: 8-B spans and a
 2-byte visMask span (1v1), 24-B spans (3v3), 48-B spans and wide rows over
 the mapped load's 512-B threshold (6v6), and world groups whose boundaries
 the restored spans cross (6v6, W = 7, three groups)."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -27,67 +26,18 @@ SHAPES = [(1, 3, 1), (3, 5, 1), (6, 3, 1), (6, 7, 3)]
 NAMES = T.STEP_OUTPUTS + T.DEBUG_OUTPUTS + ["EXPLORE"]
 
 
-def _lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    lib.mpenv_state_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mpenv_state_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
-    lib.mpenv_state_section.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.mpenv_graph_captures.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    lib.mpenv_graph_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_char_p, C.c_int32]
-    return lib
-
-
-def state_bytes(e):
-    n = C.c_int64()
-    assert _lib().mpenv_state_bytes(e.h, C.byref(n)) == 0
-    return n.value
-
-
-def state_error(e):
-    v = C.c_uint32(99)
-    assert _lib().mpenv_state_error(e.h, C.byref(v)) == 0
-    return v.value
-
-
-def save(e, buf):
-    assert _lib().mpenv_state_save(e.h, buf, None) == 0, e.lib.mpenv_last_error().decode()
-
-
-def load(e, buf, world_map=None):
-    assert _lib().mpenv_state_load(e.h, buf, world_map, None) == 0, e.lib.mpenv_last_error().decode()
-
-
-def new_blob(e):
-    return e.mem.upload(np.full(state_bytes(e), 0xA5, np.uint8))
-
-
-def graph_state(e):
-    n, on = C.c_int64(), C.c_int32()
-    assert _lib().mpenv_graph_captures(e.h, C.byref(n)) == 0
-    assert _lib().mpenv_graph_status(e.h, C.byref(on), None, 0) == 0
-    return n.value, on.value
-
-
 def row_kinds(e):
     """{output name: rows per world}, from the snapshot's own section table
     (not guessed from shape[0]: with N = 2, A == 2 W)."""
-    lib = _lib()
-    w, t, l = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    assert lib.mpenv_state_dims(e.h, C.byref(w), C.byref(t), C.byref(l)) == 0
-    per = {0: 2 * t.value, 1: 1, 2: 2}
+    w, t, l = T.state_dims(e)
+    per = {0: 2 * t, 1: 1, 2: 2}
     out = {}
     k = 0
     while True:
-        name, kind = C.c_char_p(), C.c_int32()
-        if lib.mpenv_state_section(k, w.value, t.value, l.value, C.byref(name), None, None, None,
-                                   C.byref(kind), None) != 0:
+        sec = T.state_section(k, w, t, l)
+        if sec is None:
             break
-        out[name.value.decode()] = per[kind.value]
+        out[sec["name"]] = per[sec["kind"]]
         k += 1
     # the debug exports are gathered from per-agent / per-world columns
     for n in ("DEBUG_AGENT_F32", "DEBUG_AGENT_I32", "EXPLORE"):
@@ -168,22 +118,22 @@ def test_rewind_and_replay_against_the_oracle(ts, W, groups):
     rec = oracle_run(ts, W)
     A = W * 2 * ts
     e = engine_at(ts, W, groups, 7, rec)
-    before = graph_state(e)
-    blob = new_blob(e)
-    save(e, blob)
+    before = (e.graph_captures(), e.graph_status()[0])
+    blob = e.new_state_blob()
+    e.state_save(blob)
     for s in range(8, STEPS):
         e.set_actions(tape(s, A))
         e.step()
         compare_all(outputs(e), rec[s], f"step {s}")
-    load(e, blob)
+    e.state_load(blob)
     # no step in between: every export is what it was after step 7
     compare_all(outputs(e), rec[7], "directly after the load")
     for s in range(8, STEPS):
         e.set_actions(tape(s, A))
         e.step()
         compare_all(outputs(e), rec[s], f"replayed step {s}")
-    assert state_error(e) == 0
-    assert graph_state(e) == before and before[1] == 1 and before[0] >= 1
+    assert e.state_error() == 0
+    assert (e.graph_captures(), e.graph_status()[0]) == before and before[1] == 1 and before[0] >= 1
     e.mem.free(blob)
     e.close()
 
@@ -195,8 +145,8 @@ def test_selective_restore_rewinds_some_worlds_and_keeps_the_rest(ts, W, groups)
     A = W * N
     e = engine_at(ts, W, groups, 5)
     kinds = row_kinds(e)
-    blob = new_blob(e)
-    save(e, blob)
+    blob = e.new_state_blob()
+    e.state_save(blob)
     for s in range(6, 12):
         e.set_actions(tape(s, A))
         e.step()
@@ -205,7 +155,7 @@ def test_selective_restore_rewinds_some_worlds_and_keeps_the_rest(ts, W, groups)
     wmap = np.full(W, -1, np.int32)
     wmap[rewound] = rewound
     dmap = e.mem.upload(wmap)
-    load(e, blob, dmap)
+    e.state_load(blob, dmap)
     got = outputs(e)
     compare_worlds(got, rec[5], kinds, [(w, w) for w in rewound], "after the load, rewound")
     compare_worlds(got, rec[11], kinds, [(w, w) for w in kept], "after the load, kept")
@@ -218,7 +168,7 @@ def test_selective_restore_rewinds_some_worlds_and_keeps_the_rest(ts, W, groups)
     got = outputs(e)
     compare_worlds(got, rec[6], kinds, [(w, w) for w in rewound], "one step on, rewound")
     compare_worlds(got, rec[12], kinds, [(w, w) for w in kept], "one step on, kept")
-    assert state_error(e) == 0
+    assert e.state_error() == 0
     e.mem.free(dmap)
     e.mem.free(blob)
     e.close()
@@ -241,13 +191,13 @@ def test_fork_continues_as_the_source_world_did(ts, W, groups):
             assert rec[step]["DEBUG_WORLD_I32"][s, ep_col] == rec[first - 1]["DEBUG_WORLD_I32"][s, ep_col], (s, step)
     e = engine_at(ts, W, groups, first - 1)
     kinds = row_kinds(e)
-    blob = new_blob(e)
-    save(e, blob)
+    blob = e.new_state_blob()
+    e.state_save(blob)
     wmap = np.full(W, -1, np.int32)
     for d, s in forks:
         wmap[d] = s
     dmap = e.mem.upload(wmap)
-    load(e, blob, dmap)
+    e.state_load(blob, dmap)
     source = {d: s for d, s in forks}
     pairs = [(d, source.get(d, d)) for d in range(W)]
     compare_worlds(outputs(e), rec[first - 1], kinds, pairs, "directly after the fork")
@@ -259,7 +209,7 @@ def test_fork_continues_as_the_source_world_did(ts, W, groups):
         e.set_actions(acts)
         e.step()
         compare_worlds(outputs(e), rec[step], kinds, pairs, f"forked step {step}")
-    assert state_error(e) == 0
+    assert e.state_error() == 0
     e.mem.free(dmap)
     e.mem.free(blob)
     e.close()
@@ -286,18 +236,18 @@ def test_checkpoints_under_misaligned_world_groups(what, ts, W, groups):
 def test_refused_loads_write_nothing():
     ts, W = 3, 5
     e = engine_at(ts, W, 1, 3)
-    blob = new_blob(e)
-    save(e, blob)
-    nbytes = state_bytes(e)
+    blob = e.new_state_blob()
+    e.state_save(blob)
+    nbytes = e.state_bytes()
     for s in range(4, 7):
         e.set_actions(tape(s, W * 2 * ts))
         e.step()
     before = {n: e.get(n) for n in T.DEBUG_OUTPUTS}
 
     def refused(src, world_map, bit, what):
-        load(e, src, world_map)  # the call itself succeeds: the check runs on the device
-        assert state_error(e) == bit, what
-        assert state_error(e) == 0, what
+        e.state_load(src, world_map)  # the call itself succeeds: the check runs on the device
+        assert e.state_error() == bit, what
+        assert e.state_error() == 0, what
         for n in T.DEBUG_OUTPUTS:
             assert np.array_equal(e.get(n).view(np.uint8), before[n].view(np.uint8)), (what, n)
 
@@ -312,8 +262,8 @@ def test_refused_loads_write_nothing():
         e.mem.free(dbad)
     for other_ts, other_W, what in ((ts, 3, "another W"), (1, W, "another team size")):
         o = engine_at(other_ts, other_W, 1, 0)
-        oblob = new_blob(o)
-        save(o, oblob)
+        oblob = o.new_state_blob()
+        o.state_save(oblob)
         o.mem.hip.hipDeviceSynchronize()
         refused(oblob, None, ERR_HEADER, what)
         ident = e.mem.upload(np.arange(W, dtype=np.int32))
@@ -328,18 +278,18 @@ def test_refused_loads_write_nothing():
         refused(blob, dmap, ERR_MAP, what)
         e.mem.free(dmap)
     # the snapshot itself is still good
-    load(e, blob)
-    assert state_error(e) == 0
+    e.state_load(blob)
+    assert e.state_error() == 0
     T.compare(e.get("DEBUG_AGENT_F32"), oracle_run(ts, W)[3]["DEBUG_AGENT_F32"], "good load after the refusals")
     e.mem.free(blob)
     e.close()
 
 
 def test_host_side_rejections_name_their_reason(tmp_path):
-    lib = _lib()
+    lib = T.lib_mpenv()
     e = T.Engine(3, 1)
     e.init()
-    blob = new_blob(e)
+    blob = e.new_state_blob()
 
     def invalid(rc, word):
         assert rc == -1  # MPENV_ERR_INVALID
@@ -355,7 +305,7 @@ def test_host_side_rejections_name_their_reason(tmp_path):
     invalid(lib.mpenv_state_load(e.h, blob, blob + 4, None), "aligned")
     # a buffer inside the manager's own allocations would alias live state
     invalid(lib.mpenv_state_load(e.h, e.desc("SELF_OBSERVATION")[0], None, None), "own allocations")
-    assert state_error(e) == 0
+    assert e.state_error() == 0
     logged = T.Engine(3, 1, events=str(tmp_path))
     logged.init()
     invalid(lib.mpenv_state_save(logged.h, blob, None), "event_log_path")

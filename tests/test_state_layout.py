@@ -21,33 +21,11 @@ EXEMPT = {"AGENT_MAP"}
 ELEM = {0: 4, 1: 4, 2: 4, 3: 1, 4: 2, 5: 8}
 
 
-def _lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_state_section.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.mpenv_state_section_dtype.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
-    lib.mpenv_export_layout.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    return lib
-
-
-def section(idx, W, team, track=TRACK):
-    name, off, nbytes = C.c_char_p(), C.c_int64(-1), C.c_int64(-1)
-    rb, kind, eid = C.c_int32(-1), C.c_int32(-9), C.c_int32(-9)
-    rc = _lib().mpenv_state_section(idx, W, team, track, C.byref(name), C.byref(off), C.byref(nbytes),
-                                    C.byref(rb), C.byref(kind), C.byref(eid))
-    if rc != 0:
-        return None
-    return dict(name=name.value.decode(), offset=off.value, bytes=nbytes.value, row_bytes=rb.value,
-                kind=kind.value, export_id=eid.value)
-
-
 def all_sections(W, team, track=TRACK):
-    blob = section(-1, W, team, track)
-    secs = [section(k, W, team, track) for k in range(blob["row_bytes"])]
+    blob = T.state_section(-1, W, team, track)
+    secs = [T.state_section(k, W, team, track) for k in range(blob["row_bytes"])]
     assert all(s is not None for s in secs)
-    assert section(blob["row_bytes"], W, team, track) is None  # one past the end
+    assert T.state_section(blob["row_bytes"], W, team, track) is None  # one past the end
     return blob, secs
 
 
@@ -73,7 +51,7 @@ def test_sections_are_aligned_ordered_and_sized_by_their_rows(W, team):
 
 @pytest.mark.parametrize("W,team", CONFIGS)
 def test_every_table_export_is_inside_exactly_once(W, team):
-    lib = _lib()
+    lib = T.lib_mpenv()
     _, secs = all_sections(W, team)
     by_id = {}
     for s in secs:
@@ -125,9 +103,9 @@ def test_state_columns_and_hand_allocated_buffers_are_sections():
 
 
 def test_bad_arguments_are_refused():
-    lib = _lib()
+    lib = T.lib_mpenv()
     for args in ((0, 0, 3, TRACK), (0, 3, 0, TRACK), (0, 3, 7, TRACK), (0, 3, 3, 127), (-2, 3, 3, TRACK)):
-        assert section(*args) is None, args
+        assert T.state_section(*args) is None, args
         assert lib.mpenv_last_error()
 
 
@@ -145,7 +123,7 @@ def test_python_views_of_a_cpu_blob(W, team):
     # a fake blob: byte i holds i mod 251, so a view's bytes tell its offset
     blob = (torch.arange(blob_info["bytes"], dtype=torch.int64) % 251).to(torch.uint8)
     raw = blob.numpy()
-    lib = _lib()
+    lib = T.lib_mpenv()
     for k, s in enumerate(secs):
         off, nbytes, dtype, shape = table[s["name"]]
         assert (off, nbytes) == (s["offset"], s["bytes"])

@@ -40,52 +40,6 @@ EP_COL = 11  # MPENV_DBG_WI_EPISODE_COUNTER
 NP_DTYPES = {0: np.int32, 1: np.float32, 2: np.uint32, 3: np.uint8, 4: np.uint16, 5: np.uint64}
 
 
-def _lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_wire_bytes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
-    lib.mpenv_wire_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mpenv_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    lib.mpenv_state_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mpenv_state_dims.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 3
-    lib.mpenv_state_section.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.mpenv_state_section_dtype.argtypes = [C.c_int32, C.POINTER(C.c_int32)]
-    return lib
-
-
-def wire_bytes(e, keyframe):
-    n = C.c_int64()
-    assert _lib().mpenv_wire_bytes(e.h, int(keyframe), C.byref(n)) == 0
-    return n.value
-
-
-def wire_error(e):
-    v = C.c_uint32(99)
-    assert _lib().mpenv_wire_error(e.h, C.byref(v)) == 0
-    return v.value
-
-
-def state_error(e):
-    v = C.c_uint32(99)
-    assert _lib().mpenv_state_error(e.h, C.byref(v)) == 0
-    return v.value
-
-
-def pack(e, buf, keyframe):
-    assert _lib().mpenv_wire_pack(e.h, buf, int(keyframe), None) == 0, e.lib.mpenv_last_error().decode()
-    e.mem.hip.hipDeviceSynchronize()
-
-
-def unpack(sh, buf, keyframe):
-    assert _lib().mpenv_wire_unpack(sh.h, buf, int(keyframe), None) == 0, sh.lib.mpenv_last_error().decode()
-    sh.mem.hip.hipDeviceSynchronize()
-
-
 def download(e, ptr, n):
     out = np.empty(n, np.uint8)
     e.mem.d2h(ptr, n, out)
@@ -108,25 +62,21 @@ class Snapshot:
     (mpenv_state_section)."""
 
     def __init__(self, e):
-        lib = _lib()
-        n = C.c_int64()
-        assert lib.mpenv_state_bytes(e.h, C.byref(n)) == 0
-        self.e, self.nbytes = e, n.value
+        lib = T.lib_mpenv()
+        self.e, self.nbytes = e, e.state_bytes()
         self.dev = e.mem.upload(np.full(self.nbytes, FILL, np.uint8))
-        assert lib.mpenv_state_save(e.h, self.dev, None) == 0, e.lib.mpenv_last_error().decode()
+        e.state_save(self.dev)
         e.mem.hip.hipDeviceSynchronize()
         self.host = download(e, self.dev, self.nbytes)
-        w, t, l = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        assert lib.mpenv_state_dims(e.h, C.byref(w), C.byref(t), C.byref(l)) == 0
+        dims = T.state_dims(e)
         self.sections = {}
         k = 0
         while True:
-            name, off, nb, dt = C.c_char_p(), C.c_int64(), C.c_int64(), C.c_int32()
-            if lib.mpenv_state_section(k, w.value, t.value, l.value, C.byref(name), C.byref(off), C.byref(nb), None,
-                                       None, None) != 0:
+            sec, dt = T.state_section(k, *dims), C.c_int32()
+            if sec is None:
                 break
             assert lib.mpenv_state_section_dtype(k, C.byref(dt)) == 0
-            self.sections[name.value.decode()] = (off.value, nb.value, NP_DTYPES[dt.value])
+            self.sections[sec["name"]] = (sec["offset"], sec["bytes"], NP_DTYPES[dt.value])
             k += 1
 
     def column(self, name, host=None):
@@ -137,11 +87,11 @@ class Snapshot:
         """restore the engine from this snapshot, or from an edited copy of its bytes"""
         if host is not None:
             self.e.mem.h2d(self.dev, host)
-        assert _lib().mpenv_state_load(self.e.h, self.dev, None, None) == 0, self.e.lib.mpenv_last_error().decode()
+        self.e.state_load(self.dev)
         self.e.mem.hip.hipDeviceSynchronize()
         if host is not None:
             self.e.mem.h2d(self.dev, self.host)
-        assert state_error(self.e) == 0
+        assert self.e.state_error() == 0
 
     def free(self):
         self.e.mem.free(self.dev)
@@ -184,11 +134,11 @@ def check_packed_bytes(e, snap, keyframe, world_offset, host=None):
     block, the guard -- is still FILL.  Returns (device buffer, message)."""
     A, W, N = e.W * e.N, e.W, e.N
     what = "keyframe" if keyframe else "plain"
-    n = wire_bytes(e, keyframe)
+    n = e.wire_bytes(keyframe)
     L = R.layout(A, W, keyframe)
     assert n == L["total"]
     buf = e.mem.upload(np.full(n + GUARD, FILL, np.uint8))
-    pack(e, buf, keyframe)
+    e.wire_pack(buf, keyframe)
     msg = download(e, buf, n + GUARD)
     header = R.make_header(A, W, N, N // 2, keyframe, world_offset=world_offset)
     want, mask = R.encode(wire_columns(e, snap, keyframe, host), header)
@@ -236,8 +186,8 @@ def test_pack_and_unpack_against_the_numpy_format(ts, W, world_offset, classes):
         for ex in ("FWD_LIDAR", "REAR_LIDAR", "HP", "ALIVE", "REWARD", "MAGAZINE", "REWARD_HYPER_PARAMS", "DONE",
                    "MATCH_RESULT"):
             sh.put(ex, np.full(sh.desc(ex)[2], 7))
-        unpack(sh, buf, keyframe)
-        assert wire_error(sh) == 0
+        sh.wire_unpack(buf, keyframe)
+        assert sh.wire_error() == 0
         hdr, cols = R.decode(msg)
         assert hdr == header
         got_lidar = np.concatenate([sh.get("FWD_LIDAR").reshape(A, R.FWD_RAYS, 4),
@@ -288,10 +238,10 @@ def test_round_trip_at_ragged_shapes_with_every_episode_counter_move(ts, W):
     late = T.Engine(W, ts, sim_flags=1)  # joins by keyframe at step 100
     e.put_ctrl([0, 1, 1])
     e.init()
-    buf = e.mem.upload(np.zeros(wire_bytes(e, True), np.uint8))
-    pack(e, buf, True)
-    unpack(sh, buf, True)
-    assert wire_error(sh) == 0
+    buf = e.mem.upload(np.zeros(e.wire_bytes(True), np.uint8))
+    e.wire_pack(buf, True)
+    sh.wire_unpack(buf, True)
+    assert sh.wire_error() == 0
     compare_outputs(sh, e, "init")
     e.enable_stats(True)
     # triggered resets: {step: world}, before that step
@@ -310,19 +260,19 @@ def test_round_trip_at_ragged_shapes_with_every_episode_counter_move(ts, W):
             e.put("HP", np.ones(W * 2 * ts, np.float32))
         e.set_actions(T.combat_actions(e, s))
         e.step()
-        pack(e, buf, False)
-        unpack(sh, buf, False)
+        e.wire_pack(buf, False)
+        sh.wire_unpack(buf, False)
         compare_outputs(sh, e, f"step {s}")
         if s > 100 and not (ragged and s == 150):
-            unpack(late, buf, False)
+            late.wire_unpack(buf, False)
         if s == 100 or (ragged and s == 150):
-            pack(e, buf, True)
-            unpack(late, buf, True)
+            e.wire_pack(buf, True)
+            late.wire_unpack(buf, True)
         if s >= 100:
             compare_outputs(late, e, f"step {s} (keyframe at 100)")
         ep.append(e.get("DEBUG_WORLD_I32")[:, EP_COL].copy())
         respawning += int((e.get("DEBUG_AGENT_I32")[:, 7] > 0).sum())
-    assert wire_error(sh) == 0 and wire_error(late) == 0
+    assert sh.wire_error() == 0 and late.wire_error() == 0
     ep = np.stack(ep)  # [steps + 1, W]
     # an episode counter moved by itself: in a world, at a step, without a triggered reset
     moved = [(s, w) for s in range(steps) for w in range(W) if ep[s + 1, w] != ep[s, w]]
@@ -348,13 +298,13 @@ def test_pack_flags_values_the_format_cannot_carry():
     e = sender_after_combat(ts, W)
     sh = T.Engine(W, ts, sim_flags=1)
     snap = Snapshot(e)
-    buf = e.mem.upload(np.full(wire_bytes(e, True), FILL, np.uint8))
+    buf = e.mem.upload(np.full(e.wire_bytes(True), FILL, np.uint8))
 
     def resync(where):
-        pack(e, buf, True)
+        e.wire_pack(buf, True)
         assert download(e, buf, 12)[8:12].view(np.uint32)[0] == R.FLAG_KEYFRAME, where
-        unpack(sh, buf, True)
-        assert wire_error(sh) == 0, where
+        sh.wire_unpack(buf, True)
+        assert sh.wire_error() == 0, where
         compare_outputs(sh, e, where)
 
     def weapon_256():
@@ -377,18 +327,18 @@ def test_pack_flags_values_the_format_cannot_carry():
         for keyframe in (False, True):
             corrupt()
             before = train_outputs(sh)
-            pack(e, buf, keyframe)
+            e.wire_pack(buf, keyframe)
             flags = int(download(e, buf, 12)[8:12].view(np.uint32)[0])
             assert flags == R.FLAG_OVERFLOW | (R.FLAG_KEYFRAME if keyframe else 0), (corrupt.__name__, keyframe, flags)
-            unpack(sh, buf, keyframe)
-            assert wire_error(sh) == REFUSED | DESYNC, (corrupt.__name__, keyframe)
+            sh.wire_unpack(buf, keyframe)
+            assert sh.wire_error() == REFUSED | DESYNC, (corrupt.__name__, keyframe)
             after = train_outputs(sh)
             for n in T.TRAIN_OUTPUTS:
                 assert before[n].tobytes() == after[n].tobytes(), (corrupt.__name__, keyframe, n)
             # the sender restored: its next keyframe is accepted and the shadow equals it
             snap.load()
             resync(f"after {corrupt.__name__} ({'keyframe' if keyframe else 'plain'})")
-    assert wire_error(sh) == 0
+    assert sh.wire_error() == 0
     e.mem.free(buf)
     snap.free()
     e.close()

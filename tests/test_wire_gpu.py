@@ -8,7 +8,6 @@ the shadow's own k_obs, the last-known rows from the shadow's history
 Driven at the full C3 batch with the device aim-bot (kills, respawns and
 last-known updates) and triggered resets (episode counters move), from the
 first step and from a keyframe mid-episode; plus the rejections."""
-import ctypes as C
 import time
 
 import numpy as np
@@ -22,34 +21,12 @@ RING = 64
 SEED = 1234
 
 
-def _lib():
-    lib = T.lib_mpenv()
-    lib.mpenv_wire_bytes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
-    lib.mpenv_wire_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    return lib
-
-
-def _bytes(e, keyframe):
-    n = C.c_int64()
-    assert e.lib.mpenv_wire_bytes(e.h, int(keyframe), C.byref(n)) == 0
-    return n.value
-
-
-def _error(e):
-    v = C.c_uint32(99)
-    assert e.lib.mpenv_wire_error(e.h, C.byref(v)) == 0
-    return v.value
-
-
 def _ship(e, sh, buf, keyframe):
     # pack on the sender's stream, unpack on the shadow's: the device sync
-    # in between stands in for the transfer's completion
-    assert e.lib.mpenv_wire_pack(e.h, buf, int(keyframe), None) == 0
-    e.mem.hip.hipDeviceSynchronize()
-    assert sh.lib.mpenv_wire_unpack(sh.h, buf, int(keyframe), None) == 0
-    e.mem.hip.hipDeviceSynchronize()  # read before anything packs into buf again
+    # after each stands in for the transfer's completion, and the unpack has
+    # read buf before anything packs into it again
+    e.wire_pack(buf, keyframe)
+    sh.wire_unpack(buf, keyframe)
 
 
 def _compare(e, sh, where):
@@ -63,18 +40,17 @@ def test_wire_roundtrip_full_batch_combat_and_resets():
     N = 2 * ts
     A = W * N
     t0 = time.time()
-    _lib()
     e = T.Engine(W, ts)
     sh = T.Engine(W, ts)        # the learner's shadow of e, shipped from step 0
     late = T.Engine(W, ts)      # a shadow joining at step 50 with a keyframe
     e.put_ctrl([0, 1, 1])
     e.init()
-    nb, nk = _bytes(e, False), _bytes(e, True)
+    nb, nk = e.wire_bytes(False), e.wire_bytes(True)
     assert nb < 500 * A and nk > nb
     buf = e.mem.upload(np.zeros(nk, np.uint8))
     ring = e.mem.upload(T.mpenv_tape.tape_ring(SEED, 0, A, RING))
     _ship(e, sh, buf, True)
-    assert _error(sh) == 0
+    assert sh.wire_error() == 0
     _compare(e, sh, "init")
     e.enable_stats(True)
     rng = np.random.default_rng(3)
@@ -95,7 +71,7 @@ def test_wire_roundtrip_full_batch_combat_and_resets():
             if s > 150:
                 _compare(e, late, f"step {s} (keyframe at 150)")
             print(f"  step {s}: shadows equal, test {time.time() - t0:.0f} s", flush=True)
-    assert _error(sh) == 0 and _error(late) == 0
+    assert sh.wire_error() == 0 and late.wire_error() == 0
     st = e.read_stats()
     assert st["kills"] > 0
     lk = e.get("OPPONENT_LAST_KNOWN_OBSERVATIONS")
@@ -114,40 +90,39 @@ def test_wire_rejects_foreign_or_mismatched_messages():
     messages (its history is behind) and skips its observation rows until a
     keyframe resynchronises it (a silently drifting shadow)."""
     REF, DES = 1, 2
-    _lib()
     a = T.Engine(64, 3)
     b = T.Engine(32, 3)
     c = T.Engine(64, 3, world_id_offset=64)  # the same configuration, another shard
     for x in (a, b, c):
         x.put_ctrl([0, 1, 1])
         x.init()
-    buf = a.mem.upload(np.zeros(_bytes(a, True), np.uint8))
-    kbuf = a.mem.upload(np.zeros(_bytes(a, True), np.uint8))
+    buf = a.mem.upload(np.zeros(a.wire_bytes(True), np.uint8))
+    kbuf = a.mem.upload(np.zeros(a.wire_bytes(True), np.uint8))
     assert a.lib.mpenv_wire_pack(a.h, buf, 0, None) == 0
     assert a.lib.mpenv_wire_pack(a.h, kbuf, 1, None) == 0
     a.mem.hip.hipDeviceSynchronize()
     # another configuration
     assert b.lib.mpenv_wire_unpack(b.h, buf, 0, None) == 0
-    assert _error(b) == REF | DES
+    assert b.wire_error() == REF | DES
     # another shard (header world offset 0, shadow offset 64)
     assert c.lib.mpenv_wire_unpack(c.h, buf, 0, None) == 0
-    assert _error(c) == REF | DES
+    assert c.wire_error() == REF | DES
     # a plain message unpacked as a keyframe
     assert a.lib.mpenv_wire_unpack(a.h, buf, 1, None) == 0
-    assert _error(a) == REF | DES
+    assert a.wire_error() == REF | DES
     # out of sync: the right kind is still refused
     a.step()  # the engine's own step writes its rows (no gate on the step path)
     stepped = a.get("OPPONENT_OBSERVATIONS").copy()
     assert a.lib.mpenv_wire_pack(a.h, buf, 0, None) == 0
     a.mem.hip.hipDeviceSynchronize()
     assert a.lib.mpenv_wire_unpack(a.h, buf, 0, None) == 0
-    assert _error(a) == REF | DES
-    assert _error(a) == DES  # the read cleared REFUSED only
+    assert a.wire_error() == REF | DES
+    assert a.wire_error() == DES  # the read cleared REFUSED only
     # a keyframe resynchronises; plain messages are accepted again
     assert a.lib.mpenv_wire_unpack(a.h, kbuf, 1, None) == 0
-    assert _error(a) == 0
+    assert a.wire_error() == 0
     assert a.lib.mpenv_wire_unpack(a.h, buf, 0, None) == 0
-    assert _error(a) == 0
+    assert a.wire_error() == 0
     T.compare(a.get("OPPONENT_OBSERVATIONS"), stepped, "rows rebuilt after the resync")
     a.mem.free(buf)
     a.mem.free(kbuf)
@@ -160,18 +135,13 @@ def test_learner_wire_raises_on_a_refused_message_then_recovers_at_a_keyframe():
     asynchronous check too).  The periodic keyframe (keyframe_every) then
     resynchronises the shadow: after it the outputs equal the engine's again
     (a refused message must not freeze a shadow for good)."""
-    import socket
-
     import torch
     import torch.distributed as dist
     import madrona_mp_env as m
     from mpenv_dist import LearnerWire
 
     ts, W = 3, 64
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{T.free_port()}", rank=0, world_size=1)
     try:
         def mk():
             return m.SimManager(exec_mode=m.madrona.ExecMode.CUDA, gpu_id=0, num_worlds=W, rand_seed=5,
@@ -238,8 +208,6 @@ def test_learner_wire_loopback_matches_the_engine(overlap):
     ordered by GPU events (overlap) or on the step stream -- the shadow's
     trainInterface outputs (outputs()) equal the engine's bit for bit, with
     combat actions driving kills and last-known rows."""
-    import socket
-
     import torch
     import torch.distributed as dist
     import madrona_mp_env as m
@@ -247,10 +215,7 @@ def test_learner_wire_loopback_matches_the_engine(overlap):
 
     ts, W, steps = 6, 512, 60
     A = W * 2 * ts
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{T.free_port()}", rank=0, world_size=1)
     try:
         def mk():
             return m.SimManager(exec_mode=m.madrona.ExecMode.CUDA, gpu_id=0, num_worlds=W, rand_seed=5,

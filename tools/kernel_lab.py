@@ -145,25 +145,15 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
     import mpenv_testlib as T
 
     path = os.path.join(LAB, name, "libmpenv.so") if name != "main" else os.path.join(PKG, "libmpenv.so")
-    lib = C.CDLL(path)
-    lib.mpenv_create.argtypes = [C.POINTER(T.MpenvConfig), C.POINTER(C.c_void_p)]
-    lib.mpenv_last_error.restype = C.c_char_p
-    for f in ("mpenv_init", "mpenv_step"):
-        getattr(lib, f).argtypes = [C.c_void_p]
-    lib.mpenv_enable_kernel_timing.argtypes = [C.c_void_p, C.c_int32]
-    lib.mpenv_kernel_timings.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p),
-                                         C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    lib = T.bind(C.CDLL(path))
     cfg = T.MpenvConfig(1, 0, worlds, 5, 1, 0, 2, team, 0, 0, T.SCENE.encode(), 0, None, None, None,
                         None, 0)
     h = C.c_void_p()
     assert lib.mpenv_create(C.byref(cfg), C.byref(h)) == 0, lib.mpenv_last_error()
     if os.environ.get("LAB_LIDAR_ITERS"):
         # k_lidar's tasks per wave forced (mpenv_set_lidar_iters; 0 or unset: automatic)
-        lib.mpenv_set_lidar_iters.argtypes = [C.c_void_p, C.c_int32]
         assert lib.mpenv_set_lidar_iters(h, int(os.environ["LAB_LIDAR_ITERS"])) == 0, lib.mpenv_last_error()
     # simCtrl [0, 1, 1] as bench.py (random start step and team sides)
-    lib.mpenv_export_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     hip0 = C.CDLL("libamdhip64.so")
     p, dt, nd, gid = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
     dims = (C.c_int64 * 8)()
@@ -177,10 +167,8 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
     dptr = C.c_void_p()
     assert hip.hipMalloc(C.byref(dptr), C.c_size_t(ring.nbytes)) == 0
     assert hip.hipMemcpy(dptr, ring.ctypes.data_as(C.c_void_p), C.c_size_t(ring.nbytes), 1) == 0
-    lib.mpenv_copy_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     per = ring[0].nbytes
 
-    lib.mpenv_combat_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     combat = os.environ.get("LAB_ACTIONS", "tape") == "combat"
 
     def step(s):
@@ -191,7 +179,6 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
             lib.mpenv_copy_actions(h, C.c_void_p(dptr.value + (s % 16) * per), None)
         lib.mpenv_step(h)
 
-    lib.mpenv_set_world_groups.argtypes = [C.c_void_p, C.c_int32]
     for s in range(warm):
         step(s)
     # step time with the default world groups, no timing hooks
@@ -220,8 +207,6 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
     # Output digest: variants that keep the arithmetic must agree bit-for-bit.
     import hashlib
 
-    lib.mpenv_export_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     hip.hipDeviceSynchronize()
     dig = hashlib.sha1()
     pex = {}
@@ -243,8 +228,6 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
     phases = None
     if os.environ.get("LAB_STATS"):
         # lab_hooks.patch builds with -DMPENV_LAB_PHASE_T: k_sim per-phase block cycles
-        lib.mpenv_enable_stats.argtypes = [C.c_void_p, C.c_int32]
-        lib.mpenv_read_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]
         lib.mpenv_enable_stats(h, 1)
         ns = int(os.environ.get("LAB_STATS_STEPS", 50))
         for s in range(ns):
@@ -261,13 +244,12 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
 
         nw = 1 << 16
         tb = np.zeros(2 * nw, np.uint64)
-        lib.mpenv_lab_wave.argtypes = [C.c_void_p, C.c_int32]
         lib.mpenv_set_world_groups(h, 1)
         hip.hipDeviceSynchronize()
-        lib.mpenv_lab_wave(tb.ctypes.data, nw)  # clears
+        lib.mpenv_lab_wave(C.c_void_p(tb.ctypes.data), nw)  # clears
         step(1)
         hip.hipDeviceSynchronize()
-        assert lib.mpenv_lab_wave(tb.ctypes.data, nw) == 0
+        assert lib.mpenv_lab_wave(C.c_void_p(tb.ctypes.data), nw) == 0
         tt = tb.reshape(nw, 2)
         tt = tt[tt[:, 1] > 0].astype(np.float64)
         t0 = tt[:, 0].min()
@@ -288,12 +270,11 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
 
         nthr = 1 << 18
         buf = np.zeros(11 * nthr, np.uint32)
-        lib.mpenv_lab_work.argtypes = [C.c_void_p, C.c_int32]
         hip.hipDeviceSynchronize()
-        lib.mpenv_lab_work(buf.ctypes.data, nthr)  # clears
+        lib.mpenv_lab_work(C.c_void_p(buf.ctypes.data), nthr)  # clears
         step(0)
         hip.hipDeviceSynchronize()
-        assert lib.mpenv_lab_work(buf.ctypes.data, nthr) == 0
+        assert lib.mpenv_lab_work(C.c_void_p(buf.ctypes.data), nthr) == 0
         a = worlds * 2 * team
         wv = buf.reshape(11, nthr)[:, :a].reshape(11, -1, 64).astype(np.float64)
         work = {}
@@ -313,13 +294,12 @@ def time_one(name, worlds=int(os.environ.get("LAB_WORLDS", 16384)), team=int(os.
         # per-wave sums; 5 steps)
         import numpy as np
 
-        lib.mpenv_lab_fan.argtypes = [C.c_void_p, C.c_int32]
         acc = np.zeros(13, np.float64)
         fb = np.zeros(13, np.uint64)
         for s in range(5):
             step(s)
             hip.hipDeviceSynchronize()
-            assert lib.mpenv_lab_fan(fb.ctypes.data, 13) == 0
+            assert lib.mpenv_lab_fan(C.c_void_p(fb.ctypes.data), 13) == 0
             acc += fb
         nt = max(acc[5], 1.0)
         fan = {k: round(float(acc[i]) / nt, 2) for i, k in enumerate(

@@ -37,8 +37,7 @@ SELECT, EMBED, TRUNK, ALL = 1, 2, 4, 7
 
 def measure(ts, W, ckpt):
     A = W * 2 * ts
-    lib = P.policy_lib()
-    lib.mpenv_debug_policy_step.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib = T.lib_mpenv()
     e = T.Engine(W, ts)
     hip = e.mem.hip
     hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]

@@ -37,13 +37,6 @@ def main():
     N = 2 * ts
     A = W * N
     lib = T.lib_mpenv()
-    lib.mpenv_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    lib.mpenv_state_save.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mpenv_state_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    lib.mpenv_state_section.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     e = T.Engine(W, ts)
     hip = e.mem.hip
     hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
@@ -69,9 +62,7 @@ def main():
     for s in range(40):
         e.copy_actions(ring + (s % 8) * A * 24)
         e.step()
-    n = C.c_int64()
-    ok(lib.mpenv_state_bytes(e.h, C.byref(n)))
-    nbytes = n.value
+    nbytes = e.state_bytes()
 
     def dev_alloc(size):
         p = C.c_void_p()
@@ -111,15 +102,12 @@ def main():
             ok(hip.hipEventElapsedTime(C.byref(ms), ev0, ev1))
             if rnd > 0:  # round 0 warms every variant up
                 times[name].append(ms.value / REPS)
-    err = C.c_uint32(9)
-    ok(lib.mpenv_state_error(e.h, C.byref(err)))
-    assert err.value == 0, err.value  # a refused load is a no-op and times nothing
+    err = e.state_error()
+    assert err == 0, err  # a refused load is a no-op and times nothing
 
     out = {"workload": f"{ts}v{ts} x {W} worlds after 40 tape steps", "state_bytes": nbytes,
            "sections": 0, "reps_per_round": REPS, "rounds": ROUNDS, "calls": {}}
-    sec = C.c_int32()
-    ok(lib.mpenv_state_section(-1, W, ts, 128, None, None, None, C.byref(sec), None, None))
-    out["sections"] = sec.value
+    out["sections"] = T.state_section(-1, W, ts, 128)["row_bytes"]
     for name, (_, k) in calls.items():
         ms = statistics.median(times[name])
         copied = nbytes if k == W else int(nbytes * k / W)

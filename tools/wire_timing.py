@@ -22,20 +22,14 @@ def main():
     A = W * 2 * ts
     import ctypes as C
     lib = T.lib_mpenv()
-    lib.mpenv_wire_bytes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
-    lib.mpenv_wire_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mpenv_wire_error.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     peers = int(os.environ.get("WIRE_PEERS", 7))
     nstreams = int(os.environ.get("WIRE_STREAMS", 4))
     workloads = os.environ.get("WIRE_WORKLOADS", "tape,combat").split(",")
     e = T.Engine(W, ts)
     shadows = [T.Engine(W, ts) for _ in range(peers)]
     hip = e.mem.hip
-    n = C.c_int64()
-    lib.mpenv_wire_bytes(e.h, 1, C.byref(n))
-    buf = e.mem.upload(np.zeros(n.value, np.uint8))
-    kbuf = e.mem.upload(np.zeros(n.value, np.uint8))
+    buf = e.mem.upload(np.zeros(e.wire_bytes(True), np.uint8))
+    kbuf = e.mem.upload(np.zeros(e.wire_bytes(True), np.uint8))
     ring = e.mem.upload(T.mpenv_tape.tape_ring(1234, 0, A, 64))
     streams = [C.c_void_p() for _ in range(nstreams)]
     hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
@@ -99,14 +93,13 @@ def main():
             hip.hipDeviceSynchronize()
             res[name] = round((time.perf_counter() - t0) / 40 * 1e3, 4)
         for x in shadows:  # every unpack above was accepted (a refused one is a no-op and times nothing)
-            err = C.c_uint32(9)
-            assert lib.mpenv_wire_error(x.h, C.byref(err)) == 0 and err.value == 0, err.value
+            err = x.wire_error()
+            assert err == 0, err
         res["learner_keeps_up"] = res["learner_step_ms"] <= res["sender_step_ms"]
         res["c4_scaling_bound"] = round(peers * min(1.0, res["sender_step_ms"] / res["learner_step_ms"]), 2)
         out[wl] = res
-    lib.mpenv_wire_bytes(e.h, 0, C.byref(n))
-    out["message_bytes"] = n.value
-    out["bytes_per_agent"] = round(n.value / A, 1)
+    out["message_bytes"] = e.wire_bytes(False)
+    out["bytes_per_agent"] = round(e.wire_bytes(False) / A, 1)
     out["workload"] = ("C3 6v6 x 16384, after 150 steps of each action workload (tape: the bench's action "
                        "tape; combat: the device aim-bot); unpack includes the shadow's k_obs")
     print(json.dumps(out))
