@@ -346,7 +346,29 @@ int mpenv_step(mpenv_manager *mgr);
 int mpenv_step_async(mpenv_manager *mgr, void *hip_stream);
 /* Manager::gpuStreamInit / gpuStreamStep (mgr.cpp:507-645): XLA custom-call
  * ABI.  buffers = TrainInterface inputs then outputs, in the order of
- * mpenv_train_interface(). */
+ * mpenv_train_interface().
+ *
+ * What a step leaves in the engine's own export tensors depends on its path.
+ * A direct step -- no policy loaded, and every one of the outputs fwd_lidar,
+ * rear_lidar, self, filters_state, teammates, opponents, self_pos,
+ * teammate_positions, opponent_positions, opponent_masks, agent_map and
+ * unmasked_agent_map non-null and 16-B aligned -- has the kernels write those
+ * outputs straight into the caller's buffers.  The lidar is stored twice, so
+ * the exports FWD_LIDAR and REAR_LIDAR stay current, and so does every
+ * export that is state (hp, magazine, alive, rewards, dones, episode results,
+ * the last-known rows, the full-team rows, the debug exports).  The eight
+ * observation exports SELF_OBSERVATION, FILTERS_STATE, TEAMMATE_OBSERVATIONS,
+ * OPPONENT_OBSERVATIONS, SELF_POSITION, TEAMMATE_POSITIONS,
+ * OPPONENT_POSITIONS and OPPONENT_MASKS are NOT written: they keep the
+ * content of the last plain step, copying stream step, init or state load.
+ * Until the next mpenv_step / mpenv_step_async / mpenv_init /
+ * mpenv_gpu_stream_init or copying stream step, the calls that read those
+ * rows -- mpenv_combat_actions, mpenv_state_save and mpenv_policy_load --
+ * return MPENV_ERR_INVALID and write nothing.  (mpenv_wire_pack reads state
+ * and the lidar rows only and is not affected.)
+ * A copying step -- a policy is loaded, or one of the outputs named above is
+ * null or not 16-B aligned -- writes the engine's own rows and copies every
+ * output: every export is current after it and nothing is refused. */
 int mpenv_gpu_stream_init(mpenv_manager *mgr, void *hip_stream, void **buffers);
 int mpenv_gpu_stream_step(mpenv_manager *mgr, void *hip_stream, void **buffers);
 
@@ -415,7 +437,9 @@ int mpenv_copy_actions(mpenv_manager *mgr, const int32_t *src_device, void *hip_
  * and relative yaw / pitch; mode 1 also turns and runs toward the zone when
  * no opponent is visible).  out_device [A][6] i32, or null to write the
  * step-input columns directly (as mpenv_copy_actions would).  Asynchronous
- * on hip_stream. */
+ * on hip_stream.  MPENV_ERR_INVALID, nothing written, while the last step
+ * was a direct mpenv_gpu_stream_step (which leaves the engine's observation
+ * rows behind; see there). */
 int mpenv_combat_actions(mpenv_manager *mgr, const int32_t *tape_device, int32_t *out_device, int32_t mode,
                          void *hip_stream);
 
@@ -550,7 +574,14 @@ int mpenv_wire_error_async(mpenv_manager *mgr, uint32_t *out, void *hip_stream);
  * until its next episode reset, where it draws world d's own keys (the world
  * id enters the RNG only there): forks decorrelate at episode boundaries.
  * The captured step graph is untouched (it holds pointers and sizes only).
- * mpenv_gpu_stream_step callers see restored outputs at their next step.  A
+ * mpenv_gpu_stream_step callers see restored outputs at their next step.
+ * save is refused (MPENV_ERR_INVALID, the blob untouched) while the last step
+ * was a direct mpenv_gpu_stream_step: the engine's observation rows are then
+ * those of an earlier step and the blob would break the promise above; save
+ * after a plain step.  load is accepted there and restores every row, but the
+ * host cannot know that a load was not refused on the device, so the calls a
+ * direct step blocks (mpenv_gpu_stream_step above) stay blocked until the
+ * next plain step.  A
  * LearnerWire sender's shadow does not learn of a load: its last-known
  * history is stale until the next keyframe.  A snapshot is valid only for a
  * manager with the same num_worlds, team size, scene, flags and task; it is

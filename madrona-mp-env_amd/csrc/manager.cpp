@@ -196,7 +196,10 @@ struct mpenv_manager {
     bool polLoaded = false;
     // the last step was a gpuStreamStep that wrote the observation rows into
     // its caller's buffers only (OutTab): the engine's own rows, which the
-    // policy reads, are a step behind until a step writes them again
+    // policy, the aim-bot (mpenv_combat_actions) and a snapshot
+    // (mpenv_state_save) read, are behind until a plain step, a copying
+    // gpuStreamStep or an init writes them again; those three calls are
+    // refused meanwhile (staleExports)
     bool exportsStale = false;
 
     void freePolicy()
@@ -1040,6 +1043,7 @@ int mpenv_init(mpenv_manager *m)
     if (!m) return fail(MPENV_ERR_INVALID, "null manager");
     try {
         m->runInitGraph(m->stream);
+        m->exportsStale = false;
         HIP_CHECK(hipStreamSynchronize(m->stream));
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
@@ -1120,6 +1124,17 @@ int mpenv_train_interface_entry(int32_t is_output, int32_t idx, const char **nam
     if (name) *name = tab[idx].name;
     if (export_id) *export_id = tab[idx].id;
     return MPENV_OK;
+}
+
+// The refusal of a call that reads the engine's own observation rows
+// (masks, filters, self, teammate and opponent rows, the three position
+// rows) while the last step was a direct mpenv_gpu_stream_step, which wrote
+// them into its caller's buffers only: MPENV_OK when they are current.
+static int staleExports(const mpenv_manager *m, const char *who, const char *instead)
+{
+    if (!m->exportsStale) return MPENV_OK;
+    return fail(MPENV_ERR_INVALID, std::string(who) + ": the last mpenv_gpu_stream_step wrote the observations into "
+                                       "its caller's buffers only; " + instead);
 }
 
 // cudaCopyStepInputs / cudaCopyStepOutputs (mgr.cpp:614-645): every
@@ -1208,6 +1223,7 @@ int mpenv_gpu_stream_init(mpenv_manager *m, void *stream, void **buffers)
         ensureZStream(m);
         hipStream_t st = stream ? (hipStream_t)stream : m->stream;
         m->runInitGraph(st);
+        m->exportsStale = false;
         copyTI(m, st, buffers, kSelState | kSelDirect | kSelZeros);
     } catch (const std::exception &e) {
         return fail(MPENV_ERR_HIP, e.what());
@@ -1487,6 +1503,8 @@ int mpenv_state_dims(mpenv_manager *m, uint32_t *num_worlds, uint32_t *team_size
 int mpenv_state_save(mpenv_manager *m, void *dst, void *stream)
 {
     if (int rc = stateUsable(m, dst, "state snapshot buffer")) return rc;
+    // the blob would hold observation rows from another step than its state
+    if (int rc = staleExports(m, "mpenv_state_save", "save after a plain step")) return rc;
     if (launchStateSave(m->stateTab, m->stateTabDev, static_cast<char *>(dst), stream ? stream : (void *)m->stream))
         return fail(MPENV_ERR_HIP, "state save launch failed");
     return MPENV_OK;
@@ -1496,6 +1514,11 @@ int mpenv_state_load(mpenv_manager *m, const void *src, const int32_t *map, void
 {
     if (int rc = stateUsable(m, src, "state snapshot buffer")) return rc;
     if ((uintptr_t)map & 15u) return fail(MPENV_ERR_INVALID, "state world map must be 16-B aligned");
+    // exportsStale stays as it is: the load is checked on the device and a
+    // refused one (mpenv_state_error) writes nothing, so the host cannot know
+    // that the observation rows are the blob's.  After a good load they are
+    // current and mpenv_policy_load, mpenv_combat_actions and
+    // mpenv_state_save are refused needlessly until the next plain step.
     if (launchStateLoad(m->stateTab, m->stateTabDev, static_cast<const char *>(src), map,
                         stream ? stream : (void *)m->stream))
         return fail(MPENV_ERR_HIP, "state load launch failed");
@@ -1568,10 +1591,9 @@ int mpenv_policy_load(mpenv_manager *m, const char *dir)
     if (m->cfg.sim_flags & MPENV_SIMFLAG_FULL_TEAM_POLICY)
         return fail(MPENV_ERR_INVALID, "in-sim policy inference is not available with SimFlags.FullTeamPolicy "
                                        "(the full-team action columns and the policy would write the same actions)");
-    if (m->exportsStale)
-        return fail(MPENV_ERR_INVALID, "in-sim policy inference: the last mpenv_gpu_stream_step wrote the observations "
-                                       "into its caller's buffers only; load the policy before the first "
-                                       "mpenv_gpu_stream_step or after a plain step");
+    if (int rc = staleExports(m, "in-sim policy inference",
+                              "load the policy before the first mpenv_gpu_stream_step or after a plain step"))
+        return rc;
     std::vector<float> blob;
     std::string err;
     if (const int rc = policyRead(dir, &blob, err)) return fail(rc, err);
@@ -1733,6 +1755,8 @@ int mpenv_combat_actions(mpenv_manager *m, const int32_t *tape, int32_t *out, in
 {
     if (!m || !tape) return fail(MPENV_ERR_INVALID, "null argument");
     if (mode != 0 && mode != 1) return fail(MPENV_ERR_INVALID, "combat action mode must be 0 or 1");
+    // the aim-bot would aim at the opponents of the last plain step
+    if (int rc = staleExports(m, "mpenv_combat_actions", "call it after a plain step")) return rc;
     if (launchCombatActions(m->S, tape, out, mode, stream ? stream : (void *)m->stream))
         return fail(MPENV_ERR_HIP, "combat action launch failed");
     return MPENV_OK;

@@ -454,6 +454,45 @@ def test_python_module_zero_copy_and_stream_step():
         sim.jax(False)  # no CPU (ExecMode.CPU) targets
 
 
+def test_python_module_refuses_stale_reads_after_gpu_stream_step():
+    """After sim.gpu_stream_step on the direct path the engine's own
+    observation rows are behind: sim.combat_actions and sim.save_state raise
+    with the reason and write nothing; after sim.step() they work."""
+    import torch
+    import madrona_mp_env as m
+
+    ts, W = 3, 5
+    A = W * 2 * ts
+    sim = m.SimManager(exec_mode=m.madrona.ExecMode.CUDA, gpu_id=0, num_worlds=W, rand_seed=5,
+                       auto_reset=True, sim_flags=int(m.SimFlags.Default), task_type=m.Task.Zone,
+                       team_size=ts, num_pbt_policies=0, policy_history_size=0, scene_path=T.SCENE)
+    ctrl = sim.sim_control_tensor().to_torch()
+    ctrl.copy_(torch.tensor([0, 1, 1], dtype=torch.int32, device=ctrl.device).view_as(ctrl))
+    torch.cuda.synchronize()
+    sim.init()
+    ti = sim.train_interface()
+    bufs = [t.to_torch().clone() for t in list(ti["inputs"].values()) + list(ti["outputs"].values())]
+    tape = torch.from_numpy(T.mpenv_tape.tape_actions(1234, 0, 0, A)).cuda()
+    out = torch.full((A, 6), -7, dtype=torch.int32, device="cuda")
+    blob = torch.full((sim.state_bytes(),), 0xA5, dtype=torch.uint8, device="cuda")
+    assert all(b.data_ptr() % 16 == 0 for b in bufs)  # the direct path
+    torch.cuda.synchronize()
+    sim.gpu_stream_step(0, [b.data_ptr() for b in bufs])
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match="mpenv_combat_actions.*mpenv_gpu_stream_step"):
+        sim.combat_actions(tape.data_ptr(), out.data_ptr(), 1, 0)
+    with pytest.raises(RuntimeError, match="mpenv_state_save.*mpenv_gpu_stream_step"):
+        sim.save_state(blob.data_ptr(), 0)
+    torch.cuda.synchronize()
+    assert (out == -7).all().item() and (blob == 0xA5).all().item()
+    sim.step()
+    sim.combat_actions(tape.data_ptr(), out.data_ptr(), 1, 0)
+    sim.save_state(blob.data_ptr(), 0)
+    torch.cuda.synchronize()
+    assert (out != -7).all().item()
+    assert blob[:4].cpu().numpy().tobytes() == b"MPS1"
+
+
 def test_kernel_timing_hooks():
     e = T.Engine(256, 6)
     assert e.lib.mpenv_enable_kernel_timing(e.h, 1) == 0

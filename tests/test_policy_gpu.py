@@ -314,6 +314,34 @@ def test_refusals_name_their_reason(ckpt, tmp_path):
     e.close()
 
 
+def test_load_is_refused_after_a_direct_stream_step_until_a_plain_step(ckpt):
+    """A direct mpenv_gpu_stream_step leaves the engine's own observation rows,
+    the network's inputs, a step behind: no load until a plain step."""
+    import torch
+
+    d, _ = ckpt
+    ts, W = 3, 5
+    A = W * 2 * ts
+    e = T.Engine(W, ts)
+    sb = T.StreamBuffers(e, n_sets=1)
+    e.put_ctrl([0, 1, 1])
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    e.gpu_stream_init(stream.cuda_stream, sb.arrs[0])
+    sb.set_actions(0, T.mpenv_tape.tape_actions(SEED, 0, 0, A))
+    torch.cuda.synchronize()
+    e.gpu_stream_step(stream.cuda_stream, sb.arrs[0])
+    stream.synchronize()
+    assert e.lib.mpenv_policy_load(e.h, d.encode()) == ERR_INVALID
+    assert "mpenv_gpu_stream_step" in e.lib.mpenv_last_error().decode()
+    assert loaded(e) == 0
+    e.set_actions(T.mpenv_tape.tape_actions(SEED, 1, 0, A))
+    e.step()
+    load(e, d)
+    assert loaded(e) == 1
+    e.close()
+
+
 def test_python_surface(ckpt, tmp_path):
     import torch
 
