@@ -14,6 +14,7 @@
 #ifndef MPENV_H
 #define MPENV_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -627,6 +628,16 @@ int mpenv_state_section_dtype(int32_t idx, int32_t *dtype);
  * every value equals a CPU restatement bit for bit.  The captured step graph
  * is not touched by a load or an unload.
  *
+ * Several checkpoints at once (league play): the manager has
+ * MPENV_POLICY_SLOTS = 32 slots and the agent's policy id picks the slot that
+ * evaluates it; ids whose slot is empty or that lie past the last slot fall
+ * back to slot 0 (mpenv_policy_slots.h, included below, has the rule and the
+ * per-slot calls).  The calls here are the one-checkpoint view of that:
+ * mpenv_policy_load loads into slot 0, mpenv_policy_forward evaluates slot 0,
+ * mpenv_policy_unload empties every slot and mpenv_policy_loaded says whether
+ * any slot holds a checkpoint -- so with these calls alone one checkpoint
+ * serves every policy id >= 0.
+ *
  * dir: the reference's converted-checkpoint directory, one file per tensor
  * (i32 ndim, i32 shape[ndim], f32 data; kernels [in][out]; the file names
  * loadPolicyWeights / loadNormParams open, dnn.cpp:1169-1437).
@@ -669,6 +680,9 @@ int mpenv_policy_forward(mpenv_manager *mgr, float *logits_out_device, int32_t *
 int mpenv_debug_policy_step(mpenv_manager *mgr, int32_t parts, void *hip_stream);
 int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t M, int32_t K, const float *w_host,
                              int32_t N, float *y_device, void *hip_stream);
+/* the per-slot calls: mpenv_policy_load_slot, mpenv_policy_unload_slot,
+ * mpenv_policy_slots, mpenv_policy_forward_slot */
+#include "mpenv_policy_slots.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

@@ -188,18 +188,34 @@ public:
     // extension: in-sim policy inference (mpenv.h mpenv_policy_*): while a
     // checkpoint is loaded, step() first writes the actions of every agent
     // whose AgentPolicy.idx >= 0 (evalAgentPolicy, dnn.cpp:555-891)
-    void loadPolicy(const char *dir) { check(mpenv_policy_load(mgr_, dir)); }
-    void unloadPolicy() { check(mpenv_policy_unload(mgr_)); }
+    // League play (mpenv_policy_slots.h): one checkpoint per policy id in
+    // [0, MPENV_POLICY_SLOTS); an id whose slot is empty, or past the last
+    // slot, is served by id 0's checkpoint.  Loading into an occupied id
+    // replaces that checkpoint alone.
+    void loadPolicy(const char *dir, int policyId = 0) { check(mpenv_policy_load_slot(mgr_, policyId, dir)); }
+    void unloadPolicy() { check(mpenv_policy_unload(mgr_)); } // every id
+    void unloadPolicy(int policyId) { check(mpenv_policy_unload_slot(mgr_, policyId)); }
     bool policyLoaded() const
     {
         int32_t on = 0;
         check(mpenv_policy_loaded(mgr_, &on));
         return on != 0;
     }
-    // logits [A][37] f32 and actions [A][6] i32 (or null) are device pointers
-    void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr)
+    // the policy ids that hold a checkpoint, ascending
+    std::vector<int> policySlots() const
     {
-        check(mpenv_policy_forward(mgr_, logits, actions, strm));
+        uint32_t mask = 0;
+        check(mpenv_policy_slots(mgr_, &mask));
+        std::vector<int> ids;
+        for (int s = 0; s < MPENV_POLICY_SLOTS; s++)
+            if ((mask >> s) & 1u) ids.push_back(s);
+        return ids;
+    }
+    // logits [A][37] f32 and actions [A][6] i32 (or null) are device pointers;
+    // every agent through policyId's checkpoint
+    void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
+    {
+        check(mpenv_policy_forward_slot(mgr_, policyId, logits, actions, strm));
     }
 
     // extension: world checkpoints (mpenv.h mpenv_state_*).  snapshot / worldMap

@@ -29,6 +29,7 @@ ORACLE_LIB = os.path.join(ORACLE, "_build", "liboracle.so")
 LIB_SOURCES = ["kernels.hip", "wire.hip", "state.hip", "policy.hip", "manager.cpp", "policy.cpp", "scene.cpp",
                "navmesh.cpp"]
 LIB_HEADERS = ["mpenv_core.h", "engine.h", "geom_dev.h", "scene.h", "policy.h"]
+API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h")]
 
 
 def _stale(out, deps):
@@ -46,7 +47,7 @@ def _run(cmd):
 
 def build_lib(force=False):
     srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in LIB_HEADERS] + [os.path.join(INCLUDE, "mpenv.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in LIB_HEADERS] + API_HEADERS
     if not force and not _stale(LIB, deps):
         return LIB
     objdir = os.path.join(PKG, "build")
@@ -72,7 +73,7 @@ def build_ext(force=False):
     src = os.path.join(CSRC, "pybind_module.cpp")
     if not os.path.exists(src):
         return None
-    if not force and not _stale(EXT, [src, LIB, os.path.join(INCLUDE, "mpenv.h")]):
+    if not force and not _stale(EXT, [src, LIB] + API_HEADERS):
         return EXT
     import pybind11
     py_inc = sysconfig.get_paths()["include"]
@@ -88,8 +89,7 @@ HEADLESS = os.path.join(PKG, "headless")
 def build_headless(force=False):
     """C++ driver over include/mpenv_manager.hpp (reference src/headless.cpp role)."""
     src = os.path.join(CSRC, "headless.cpp")
-    deps = [src, LIB, os.path.join(INCLUDE, "mpenv.h"), os.path.join(INCLUDE, "mpenv_manager.hpp"),
-            os.path.join(CSRC, "mpenv_core.h")]
+    deps = [src, LIB, os.path.join(INCLUDE, "mpenv_manager.hpp"), os.path.join(CSRC, "mpenv_core.h")] + API_HEADERS
     if not force and not _stale(HEADLESS, deps):
         return HEADLESS
     _run([HIPCC, "-x", "c++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",

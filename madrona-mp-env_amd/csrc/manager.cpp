@@ -190,9 +190,14 @@ struct mpenv_manager {
     StateTab *stateTabDev = nullptr;
     const char *stateRefused = nullptr;
     // In-sim policy inference (policy.hip; DESIGN.md §2 definition 15): the
-    // parameter blob and work buffers live from load to unload; while
-    // polLoaded, every step first writes the policy agents' actions
+    // one parameter blob per occupied checkpoint slot (polBlobs, the host's
+    // copy of the device table polDev.blobs; polDev.mask says which); the
+    // table and the work buffers live from the first load to the last
+    // unload; while any slot is occupied (polLoaded), every step first
+    // writes the served agents' actions
     PolicyDev polDev {};
+    const float *polBlobs[pol::kSlots] = {};
+    int32_t *polTab = nullptr; // the allocation behind polDev's counters and tile tables
     bool polLoaded = false;
     // the last step was a gpuStreamStep that wrote the observation rows into
     // its caller's buffers only (OutTab): the engine's own rows, which the
@@ -205,9 +210,50 @@ struct mpenv_manager {
     void freePolicy()
     {
         polLoaded = false;
-        for (void *p : { (void *)polDev.blob, (void *)polDev.emb, (void *)polDev.list, (void *)polDev.count })
+        for (const float *&b : polBlobs) {
+            if (b) (void)hipFree((void *)b);
+            b = nullptr;
+        }
+        for (void *p : { (void *)polDev.blobs, (void *)polDev.emb, (void *)polDev.list, (void *)polTab })
             if (p) (void)hipFree(p);
         polDev = PolicyDev {};
+        polTab = nullptr;
+    }
+
+    // The slot table (all empty), the list, the embeddings and the selection's
+    // counters and tile tables (policy.h), zeroed: the first load.
+    void allocPolicyWork()
+    {
+        auto dev = [&](size_t bytes) {
+            void *p = nullptr;
+            HIP_CHECK(hipMalloc(&p, bytes));
+            HIP_CHECK(hipMemsetAsync(p, 0, bytes, stream));
+            return p;
+        };
+        const int64_t rows = pol::listRows(S.A);
+        polDev.blobs = static_cast<const float *const *>(dev(pol::kSlots * sizeof(float *)));
+        polDev.emb = static_cast<float *>(dev((size_t)rows * pol::kTrunkIn * sizeof(float)));
+        polDev.list = static_cast<int32_t *>(dev((size_t)rows * sizeof(int32_t)));
+        polTab = static_cast<int32_t *>(dev((size_t)pol::tabBytes(S.A)));
+        polDev.count = polTab;
+        polDev.cursor = polTab + pol::kSlots;
+        polDev.tiles = reinterpret_cast<pol::Tile *>(polTab + 2 * pol::kSlots);
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    // Slot `slot` holds `blob` (device memory, owned from here on) or, null,
+    // nothing; the old blob is freed.  The caller has waited for whatever may
+    // still read the table or the old blob.
+    void setPolicySlot(int slot, const float *blob)
+    {
+        // the last selection's tiles name blobs as they were: every tile dies here (rows = 0), so
+        // the trunk alone (mpenv_debug_policy_step) never follows one to a freed blob
+        HIP_CHECK(hipMemsetAsync(polTab, 0, (size_t)pol::tabBytes(S.A), stream));
+        upload((void *)(polDev.blobs + slot), &blob, sizeof(blob));
+        if (polBlobs[slot]) (void)hipFree((void *)polBlobs[slot]);
+        polBlobs[slot] = blob;
+        polDev.mask = blob ? polDev.mask | (1u << slot) : polDev.mask & ~(1u << slot);
+        polLoaded = polDev.mask != 0;
     }
 
     ~mpenv_manager()
@@ -1582,9 +1628,19 @@ int mpenv_policy_check(const char *dir)
     return rc == MPENV_OK ? MPENV_OK : fail(rc, err);
 }
 
-int mpenv_policy_load(mpenv_manager *m, const char *dir)
+static_assert(MPENV_POLICY_SLOTS == pol::kSlots, "mpenv_policy_slots.h and policy.h name the same slots");
+
+static int policySlotRange(int32_t slot)
+{
+    if (slot >= 0 && slot < MPENV_POLICY_SLOTS) return MPENV_OK;
+    return fail(MPENV_ERR_INVALID, "policy slot " + std::to_string(slot) + " is outside [0, " +
+                                       std::to_string(MPENV_POLICY_SLOTS) + ")");
+}
+
+int mpenv_policy_load_slot(mpenv_manager *m, int32_t slot, const char *dir)
 {
     if (!m || !dir) return fail(MPENV_ERR_INVALID, "null argument");
+    if (int rc = policySlotRange(slot)) return rc;
     if (m->stateRefused)
         return fail(MPENV_ERR_INVALID, std::string("in-sim policy inference is not available for ") + m->stateRefused +
                                            " (the logged actions would not be the ones played)");
@@ -1597,25 +1653,39 @@ int mpenv_policy_load(mpenv_manager *m, const char *dir)
     std::vector<float> blob;
     std::string err;
     if (const int rc = policyRead(dir, &blob, err)) return fail(rc, err);
+    // from here on only a HIP failure stops the load; the slot keeps its old
+    // checkpoint until the new one is in device memory
+    void *fresh = nullptr;
     try {
         HIP_CHECK(hipSetDevice(m->gpu));
         HIP_CHECK(hipStreamSynchronize(m->stream));
-        m->freePolicy();
-        auto dev = [&](size_t bytes) {
-            void *p = nullptr;
-            HIP_CHECK(hipMalloc(&p, bytes));
-            return p;
-        };
-        m->polDev.blob = static_cast<const float *>(dev(blob.size() * sizeof(float)));
-        m->polDev.emb = static_cast<float *>(dev((size_t)m->S.A * pol::kTrunkIn * sizeof(float)));
-        m->polDev.list = static_cast<int32_t *>(dev((size_t)m->S.A * sizeof(int32_t)));
-        m->polDev.count = static_cast<int32_t *>(dev(16));
-        m->upload((void *)m->polDev.blob, blob.data(), blob.size() * sizeof(float));
-        m->polLoaded = true;
+        HIP_CHECK(hipMalloc(&fresh, blob.size() * sizeof(float)));
+        m->upload(fresh, blob.data(), blob.size() * sizeof(float));
+        if (!m->polDev.blobs) m->allocPolicyWork();
+        m->setPolicySlot(slot, static_cast<const float *>(fresh));
     } catch (const std::exception &e) {
-        m->freePolicy();
+        if (fresh && m->polBlobs[slot] != fresh) (void)hipFree(fresh);
+        if (!m->polDev.mask) m->freePolicy();
         return fail(MPENV_ERR_HIP, e.what());
     }
+    return MPENV_OK;
+}
+
+int mpenv_policy_load(mpenv_manager *m, const char *dir) { return mpenv_policy_load_slot(m, 0, dir); }
+
+int mpenv_policy_unload_slot(mpenv_manager *m, int32_t slot)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null manager");
+    if (int rc = policySlotRange(slot)) return rc;
+    if (!m->polBlobs[slot]) return MPENV_OK;
+    try {
+        HIP_CHECK(hipSetDevice(m->gpu));
+        HIP_CHECK(hipDeviceSynchronize()); // a step on a caller's stream may still read the blob
+        m->setPolicySlot(slot, nullptr);
+    } catch (const std::exception &e) {
+        return fail(MPENV_ERR_HIP, e.what());
+    }
+    if (!m->polDev.mask) m->freePolicy();
     return MPENV_OK;
 }
 
@@ -1623,7 +1693,7 @@ int mpenv_policy_unload(mpenv_manager *m)
 {
     if (!m) return fail(MPENV_ERR_INVALID, "null manager");
     (void)hipSetDevice(m->gpu);
-    (void)hipDeviceSynchronize(); // a step on a caller's stream may still read the blob
+    (void)hipDeviceSynchronize(); // a step on a caller's stream may still read the blobs
     m->freePolicy();
     return MPENV_OK;
 }
@@ -1635,13 +1705,29 @@ int mpenv_policy_loaded(mpenv_manager *m, int32_t *on)
     return MPENV_OK;
 }
 
-int mpenv_policy_forward(mpenv_manager *m, float *logits, int32_t *actions, void *stream)
+int mpenv_policy_slots(mpenv_manager *m, uint32_t *mask)
+{
+    if (!m || !mask) return fail(MPENV_ERR_INVALID, "null argument");
+    *mask = m->polDev.mask;
+    return MPENV_OK;
+}
+
+int mpenv_policy_forward_slot(mpenv_manager *m, int32_t slot, float *logits, int32_t *actions, void *stream)
 {
     if (!m || !logits) return fail(MPENV_ERR_INVALID, "null argument");
-    if (!m->polLoaded) return fail(MPENV_ERR_INVALID, "no policy loaded (mpenv_policy_load)");
-    if (launchPolicyForward(m->S, m->polDev, logits, actions, stream ? stream : (void *)m->stream))
+    if (int rc = policySlotRange(slot)) return rc;
+    if (!m->polBlobs[slot])
+        return fail(MPENV_ERR_INVALID, slot == 0 ? std::string("no policy loaded (mpenv_policy_load)")
+                                                 : "policy slot " + std::to_string(slot) +
+                                                       " is empty (mpenv_policy_load_slot)");
+    if (launchPolicyForward(m->S, m->polDev, slot, logits, actions, stream ? stream : (void *)m->stream))
         return fail(MPENV_ERR_HIP, "policy launch failed");
     return MPENV_OK;
+}
+
+int mpenv_policy_forward(mpenv_manager *m, float *logits, int32_t *actions, void *stream)
+{
+    return mpenv_policy_forward_slot(m, 0, logits, actions, stream);
 }
 
 int mpenv_debug_policy_step(mpenv_manager *m, int32_t parts, void *stream)

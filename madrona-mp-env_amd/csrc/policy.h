@@ -91,19 +91,48 @@ void packB(const float *w /*[K][N]*/, int K, int N, float *out /*packedFloats(K,
 int policyRead(const char *dir, std::vector<float> *blob, std::string &err);
 
 // policy.hip
-struct PolicyDev {
-    const float *blob;   // pol::layout()
-    float *emb;          // [A][384] trunk inputs of the selected agents, by list position
-    int32_t *list;       // [A] selected agent ids
-    int32_t *count;      // device word: how many
+//
+// Checkpoint slots (MPENV_POLICY_SLOTS): an agent with policy id p >= 0 is
+// served by slot p if 0 <= p < 32 and that slot holds a checkpoint, else by
+// slot 0 if that holds one, else by nobody.  The selected agents are listed by
+// slot, each slot's segment starting at a multiple of pol::kSegAlign list
+// positions (one trunk tile, a multiple of the embed kernel's agents per
+// block), so no embed wave and no trunk tile mixes checkpoints; the tail
+// positions of a segment are dead (read as zeros, write nothing).
+namespace pol {
+constexpr int kSlots = 32;
+constexpr int kSegAlign = 64;
+// list positions / emb rows that hold any selection of A agents: the sum of
+// the padded segments is a multiple of kSegAlign and at most A + 32 * 63
+constexpr int64_t listTiles(int64_t A) { return (A + (int64_t)kSlots * (kSegAlign - 1)) / kSegAlign; }
+constexpr int64_t listRows(int64_t A) { return listTiles(A) * kSegAlign; }
+// one 64-row tile of the list: all an embed or trunk block needs, in one 16-B load
+struct alignas(16) Tile {
+    const float *blob;   // the checkpoint of the tile's slot
+    int32_t rows;        // live rows: 64 but for a segment's last tile, 0 past the last segment
+    int32_t slot;
 };
-// The step path: select policy >= 0, write their action columns, advance their RNG by 6.
+// the allocation behind PolicyDev's counters and tiles: count[32], cursor[32], then the tiles
+constexpr int64_t kTabHeadBytes = 2 * kSlots * sizeof(int32_t);
+constexpr int64_t tabBytes(int64_t A) { return kTabHeadBytes + listTiles(A) * (int64_t)sizeof(Tile); }
+} // namespace pol
+
+struct PolicyDev {
+    const float *const *blobs; // [32] device table: slot -> pol::layout() blob, null while empty
+    uint32_t mask;       // bit s: slot s holds a checkpoint (the host's copy of blobs[s] != null)
+    float *emb;          // [listRows(A)][384] trunk inputs of the selected agents, by list position
+    int32_t *list;       // [listRows(A)] selected agent ids, by slot
+    int32_t *count;      // [32] agents per slot (zeroed in front of every selection)
+    int32_t *cursor;     // [32] next free list position of each segment
+    pol::Tile *tiles;    // [listTiles(A)] every tile, the dead ones behind the last segment included
+};
+// The step path: select the agents a slot serves, write their action columns, advance their RNG by 6.
 // parts: which of its kernels run (all in a step; mpenv_debug_policy_step times them apart --
 // the trunk alone reuses the list and the embeddings of the last full call).
 enum PolicyParts { kPolicySelect = 1, kPolicyEmbed = 2, kPolicyTrunk = 4, kPolicyAll = 7 };
 int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts = kPolicyAll);
-// Every agent, no engine state written: logits [A][37], actions [A][6] (or null).
-int launchPolicyForward(const DevState &s, const PolicyDev &p, float *logits, int32_t *actions, void *stream);
+// Every agent through the checkpoint of `slot`, no engine state written: logits [A][37], actions [A][6] (or null).
+int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream);
 // y[M][N] = x[M][K] . w through the trunk's MFMA dense; wPacked = pol::packB(w) in device memory.
 int launchPolicyDense(const float *x, int M, int K, const float *wPacked, int N, float *y, void *stream);
 

@@ -1,13 +1,24 @@
 // policy.hip — in-sim policy inference on gfx950 (DESIGN.md §2 definition 15,
 // §4 "Policy kernels"): the reference's evalAgentPolicy (src/dnn.cpp:555-891,
-// CPU only there) as three kernels on the step's stream.
+// CPU only there) on the step's stream: three small selection kernels, then
+// the two that compute.
 //
-//   k_pol_select  ids of the agents with policy >= 0, compacted (ballot +
-//                 prefix, one atomic per wave), so cost follows their number
+//   k_pol_count   how many agents each checkpoint slot serves (policy.h: slot
+//                 p, else slot 0, else nobody): one ballot per slot present in
+//                 a wave into the block's LDS histogram, one global atomic per
+//                 slot present in the block
+//   k_pol_plan    one wave: the 32 counts into segment bases padded to 64 list
+//                 positions, and per 64-row tile its blob, live rows and slot
+//   k_pol_scatter agent ids into their slot's segment (ballot + prefix in the
+//                 wave, LDS atomic in the block, one global atomic per slot and
+//                 block); the order inside a segment differs from run to run
+//                 and no result depends on it
 //   k_pol_embed   normalisation, position embedding and the 20 embeddings of
 //                 four agents per wave (lane = output feature, explicit fmaf
 //                 chains on the VALU); 384 floats per agent
-//   k_pol_trunk   64 agents per block, activations resident in LDS: the three
+//                 (a block's 16 list positions lie in one tile, so one slot)
+//   k_pol_trunk   one tile of 64 agents per block, the blob of the tile's slot,
+//                 activations resident in LDS: the three
 //                 512-wide layers and both heads on v_mfma_f32_32x32x2_f32,
 //                 LayerNorm statistics one row per lane, Gumbel-max sampling
 //                 on the agent lanes
@@ -15,6 +26,9 @@
 // Every dense output is one k-ascending fmaf chain from +0: the f32-input
 // MFMA computes exactly that (one rounding per product, k order), K is never
 // split across accumulators or waves, and zero padding of K is exact.
+//
+// Counts, bases and the tile tables are written by one kernel and read by the
+// next: the kernel boundary on the stream is the only ordering relied on.
 #include <hip/hip_runtime.h>
 
 #include "policy.h"
@@ -26,8 +40,14 @@ using namespace pol;
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// A checkpoint's parameters.  The blob pointer comes out of a table in memory,
+// where the compiler cannot see that it points to global memory and would read
+// through it with flat loads (which also count as LDS traffic and stall the
+// operand prefetch behind the LDS reads); the type says it.
+typedef const __attribute__((address_space(1))) float *BlobPtr;
 
 constexpr int kTileRows = 64;       // agents per trunk block
+static_assert(kTileRows == kSegAlign, "a slot's segment starts on a trunk tile");
 constexpr int kLdx = 514;           // LDS row stride in floats: row r starts at bank 2 r, so the A-operand
                                     // read (32 rows x 2 adjacent k) touches 64 different banks
 constexpr int kTrunkThreads = 512;  // 8 waves, 64 output columns each
@@ -38,6 +58,7 @@ constexpr int kEmbedAgents = 4;     // agents per wave of k_pol_embed
 constexpr int kEmbedWaves = 4;
 constexpr int kEmbedRowsMax = kEmbedAgents * kOppSlots; // 24
 constexpr int kYStride = 65;
+static_assert(kSegAlign % (kEmbedWaves * kEmbedAgents) == 0, "an embed block never straddles two segments");
 
 __device__ __forceinline__ float negInf() { return mp::u2f(0xff800000u); }
 
@@ -47,12 +68,12 @@ __device__ __forceinline__ float negInf() { return mp::u2f(0xff800000u); }
 // k step accumulates into the same registers, so each output is the chain
 // fma(a_k, b_k, ...) over k ascending.
 template <int MT, int NT>
-__device__ __forceinline__ void mfmaDense(const float *xs, int row0, int ksteps, const float *wp, f32x16 (&acc)[MT][NT])
+__device__ __forceinline__ void mfmaDense(const float *xs, int row0, int ksteps, BlobPtr wp, f32x16 (&acc)[MT][NT])
 {
     constexpr int U = 8; // k steps per chunk: the next chunk's operands are loaded while this one's MFMAs run
     const int lane = threadIdx.x & 63;
     const float *xa = xs + (row0 + (lane & 31)) * kLdx + (lane >> 5);
-    const float *wb = wp + lane;
+    const BlobPtr wb = wp + lane;
     const int64_t tileStride = (int64_t)ksteps * 64;
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
@@ -141,24 +162,95 @@ __device__ int32_t sampleHead(const float *lg, int nb, mp::RandKey k)
     return best;
 }
 
-__global__ void __launch_bounds__(256) k_pol_select(DevState S, int32_t *list, int32_t *count)
+// ---- selection ------------------------------------------------------------
+
+// the slot that serves policy id p while the slots of `mask` hold checkpoints, or -1
+__device__ __forceinline__ int slotOf(int32_t p, uint32_t mask)
 {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < 0) return -1;
+    if (p < kSlots && ((mask >> p) & 1u)) return p;
+    return (mask & 1u) ? 0 : -1;
+}
+
+// fn(s, lanes) once for every slot s present in the wave, lanes = who has it
+template <typename F>
+__device__ __forceinline__ void forEachSlotOfWave(int slot, F fn)
+{
+    unsigned long long rest = __ballot(slot >= 0);
+    while (rest) {
+        const int s = __shfl(slot, __ffsll(rest) - 1);
+        const unsigned long long same = __ballot(slot == s);
+        fn(s, same);
+        rest &= ~same;
+    }
+}
+
+constexpr int kSelThreads = 1024; // a large block: its LDS histogram leaves one global atomic per slot and block
+
+__global__ void __launch_bounds__(kSelThreads) k_pol_count(DevState S, PolicyDev P)
+{
+    __shared__ int32_t hist[kSlots]; // the block's agents per slot
+    if (threadIdx.x < kSlots) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * kSelThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const bool on = g < S.A && S.policy[g] >= 0;
-    const unsigned long long b = __ballot(on);
-    if (b == 0) return;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(count, (int)__popcll(b));
-    base = __shfl(base, 0);
-    if (on) list[base + (int)__popcll(b & ((1ull << lane) - 1ull))] = (int32_t)g;
+    const int slot = g < S.A ? slotOf(S.policy[g], P.mask) : -1;
+    forEachSlotOfWave(slot, [&](int s, unsigned long long same) {
+        if (lane == 0) atomicAdd(&hist[s], (int)__popcll(same));
+    });
+    __syncthreads();
+    if (threadIdx.x < kSlots && hist[threadIdx.x] > 0) atomicAdd(P.count + threadIdx.x, hist[threadIdx.x]);
+}
+
+// One wave.  Every one of the numTiles tiles is written: the live ones, then rows = 0.
+__global__ void __launch_bounds__(64) k_pol_plan(PolicyDev P, int numTiles)
+{
+    const int lane = threadIdx.x;
+    const int c = lane < kSlots ? P.count[lane] : 0;
+    const int padded = (c + kSegAlign - 1) / kSegAlign * kSegAlign;
+    int end = padded; // inclusive prefix sum over the lanes
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(end, d);
+        if (lane >= d) end += up;
+    }
+    const int base = end - padded;
+    if (lane < kSlots) P.cursor[lane] = base;
+    for (int s = 0; s < kSlots; s++) { // the tiles of segment s, a tile per lane
+        const int sc = __shfl(c, s), t0 = __shfl(base, s) / kSegAlign;
+        if (sc == 0) continue;
+        const float *blob = P.blobs[s];
+        for (int t = lane; t * kSegAlign < sc; t += 64) P.tiles[t0 + t] = Tile { blob, min(kSegAlign, sc - t * kSegAlign), s };
+    }
+    for (int t = __shfl(end, 63) / kSegAlign + lane; t < numTiles; t += 64) P.tiles[t] = Tile { nullptr, 0, 0 };
+}
+
+__global__ void __launch_bounds__(kSelThreads) k_pol_scatter(DevState S, PolicyDev P)
+{
+    __shared__ int32_t hist[kSlots]; // the block's agents per slot, then the block's base in that slot's segment
+    if (threadIdx.x < kSlots) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * kSelThreads + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int slot = g < S.A ? slotOf(S.policy[g], P.mask) : -1;
+    int at = 0; // this agent among the block's agents of its slot
+    forEachSlotOfWave(slot, [&](int s, unsigned long long same) {
+        int off = 0;
+        if (lane == 0) off = atomicAdd(&hist[s], (int)__popcll(same));
+        off = __shfl(off, 0);
+        if (slot == s) at = off + (int)__popcll(same & ((1ull << lane) - 1ull));
+    });
+    __syncthreads();
+    if (threadIdx.x < kSlots && hist[threadIdx.x] > 0)
+        hist[threadIdx.x] = atomicAdd(P.cursor + threadIdx.x, hist[threadIdx.x]);
+    __syncthreads();
+    if (slot >= 0) P.list[hist[slot] + at] = (int32_t)g;
 }
 
 // ---- k_pol_embed -----------------------------------------------------------
 
 // invStd * (x - mean) for `len` consecutive floats of one agent (the
 // normalize*Ob functions, dnn.cpp:193-379; parameters repeat every `period`)
-__device__ __forceinline__ void normSpan(const float *blob, const Layout &L, const float *src, int len, int param,
+__device__ __forceinline__ void normSpan(BlobPtr blob, const Layout &L, const float *src, int len, int param,
                                          int period, float *dst, bool live)
 {
     const int lane = threadIdx.x & 63;
@@ -170,7 +262,7 @@ __device__ __forceinline__ void normSpan(const float *blob, const Layout &L, con
 }
 
 template <int R>
-__device__ __forceinline__ void embedDense(const float *W, const float *xin, int K, float (&acc)[R])
+__device__ __forceinline__ void embedDense(BlobPtr W, const float *xin, int K, float (&acc)[R])
 {
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -200,8 +292,7 @@ __device__ __forceinline__ void embedDense(const float *W, const float *xin, int
 // (evalFullyConnectedLayerWithLayerNormWithActivation, dnn.cpp:428-524): the
 // Welford pass over the 64 outputs in index order runs one row per lane.
 template <int R>
-__device__ __forceinline__ void embedNorm(float (&acc)[R], float *ybuf, float *stat, const float *scale,
-                                          const float *bias)
+__device__ __forceinline__ void embedNorm(float (&acc)[R], float *ybuf, float *stat, BlobPtr scale, BlobPtr bias)
 {
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -234,18 +325,30 @@ __device__ __forceinline__ void embedNorm(float (&acc)[R], float *ybuf, float *s
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(kEmbedWaves * 64) k_pol_embed(DevState S, PolicyDev P, Layout L, int useList)
+// fwdSlot < 0: the step path, the list by tile.  Otherwise
+// every agent through the checkpoint of slot fwdSlot.
+__global__ void __launch_bounds__(kEmbedWaves * 64) k_pol_embed(DevState S, PolicyDev P, Layout L, int fwdSlot)
 {
     constexpr int G = kEmbedAgents;
     __shared__ __attribute__((aligned(16))) float s_xin[kEmbedWaves][G * kFwdIn];
     __shared__ float s_y[kEmbedWaves][kEmbedRowsMax * kYStride];
     __shared__ float s_stat[kEmbedWaves][2 * kEmbedRowsMax];
 
-    const int64_t n = useList ? (int64_t)*P.count : S.A;
-    if ((int64_t)blockIdx.x * (kEmbedWaves * G) >= n) return; // the whole block (uniform)
+    const bool useList = fwdSlot < 0;
+    const int64_t pos0 = (int64_t)blockIdx.x * (kEmbedWaves * G);
+    int64_t n = S.A; // one past the block's last live position
+    BlobPtr blob;
+    if (useList) {
+        const int64_t tile = pos0 / kTileRows;
+        const Tile t = P.tiles[tile];
+        blob = (BlobPtr)t.blob;
+        n = tile * kTileRows + t.rows;
+    } else {
+        blob = (BlobPtr)P.blobs[fwdSlot];
+    }
+    if (pos0 >= n) return; // the whole block (uniform): past the list, or the dead tail of a segment
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float *xin = s_xin[wave], *ybuf = s_y[wave], *stat = s_stat[wave];
-    const float *blob = P.blob;
 
     int64_t pos[G], agent[G];
     bool live[G];
@@ -362,10 +465,11 @@ __global__ void __launch_bounds__(kEmbedWaves * 64) k_pol_embed(DevState S, Poli
 
 // ---- k_pol_trunk -----------------------------------------------------------
 
-// useList: the step path (agents P.list[0 .. *P.count), actions into the
-// engine's columns, RNG advanced by 6).  Otherwise every agent, logits /
-// actions into the caller's buffers and no engine state written.
-__global__ void __launch_bounds__(kTrunkThreads) k_pol_trunk(DevState S, PolicyDev P, Layout L, int useList,
+// fwdSlot < 0: the step path (tile blockIdx.x of P.list, the blob of its slot,
+// actions into the engine's columns, RNG advanced by 6).  Otherwise every
+// agent through slot fwdSlot, logits / actions into the caller's buffers and
+// no engine state written.
+__global__ void __launch_bounds__(kTrunkThreads) k_pol_trunk(DevState S, PolicyDev P, Layout L, int fwdSlot,
                                                              float *logitsOut, int32_t *actionsOut)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -373,11 +477,19 @@ __global__ void __launch_bounds__(kTrunkThreads) k_pol_trunk(DevState S, PolicyD
     float *rcp = lds + kTileRows * kLdx;      // 1 / (i + 1)
     float *stat = rcp + kHidden;              // mean, sigma per row
 
-    const int64_t n = useList ? (int64_t)*P.count : S.A;
+    const bool useList = fwdSlot < 0;
     const int64_t base = (int64_t)blockIdx.x * kTileRows;
-    if (base >= n) return;
+    int64_t n = S.A; // one past the tile's last live row
+    BlobPtr blob;
+    if (useList) {
+        const Tile t = P.tiles[blockIdx.x];
+        blob = (BlobPtr)t.blob;
+        n = base + t.rows;
+    } else {
+        blob = (BlobPtr)P.blobs[fwdSlot];
+    }
+    if (base >= n) return; // past the list
     const int tid = threadIdx.x, wave = tid >> 6;
-    const float *blob = P.blob;
 
     rcp[tid] = 1.f / (float)(tid + 1);
     for (int idx = tid; idx < kTileRows * kTrunkIn; idx += kTrunkThreads) {
@@ -476,7 +588,7 @@ __global__ void __launch_bounds__(64) k_pol_dense(const float *x, int M, int K, 
     }
     __syncthreads();
     f32x16 acc[2][2];
-    mfmaDense<2, 2>(lds, 0, Kp / 2, wp + (int64_t)(2 * blockIdx.y) * (Kp / 2) * 64, acc);
+    mfmaDense<2, 2>(lds, 0, Kp / 2, (BlobPtr)wp + (int64_t)(2 * blockIdx.y) * (Kp / 2) * 64, acc);
 #pragma unroll
     for (int mt = 0; mt < 2; mt++)
 #pragma unroll
@@ -491,7 +603,7 @@ __global__ void __launch_bounds__(64) k_pol_dense(const float *x, int M, int K, 
 
 int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
 
-int run(const DevState &s, const PolicyDev &p, int useList, float *logits, int32_t *actions, hipStream_t st,
+int run(const DevState &s, const PolicyDev &p, int fwdSlot, float *logits, int32_t *actions, hipStream_t st,
         int parts = kPolicyEmbed | kPolicyTrunk)
 {
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_pol_trunk), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -499,13 +611,14 @@ int run(const DevState &s, const PolicyDev &p, int useList, float *logits, int32
         return -1;
     const Layout L = layout();
     const int64_t perBlock = kEmbedWaves * kEmbedAgents;
+    const int64_t rows = fwdSlot < 0 ? listRows(s.A) : s.A; // blocks past the last segment leave at once
     if (parts & kPolicyEmbed)
-        hipLaunchKernelGGL(k_pol_embed, dim3((unsigned)((s.A + perBlock - 1) / perBlock)), dim3(kEmbedWaves * 64), 0,
-                           st, s, p, L, useList);
+        hipLaunchKernelGGL(k_pol_embed, dim3((unsigned)((rows + perBlock - 1) / perBlock)), dim3(kEmbedWaves * 64), 0,
+                           st, s, p, L, fwdSlot);
     if (check(hipGetLastError())) return -1;
     if (!(parts & kPolicyTrunk)) return 0;
-    hipLaunchKernelGGL(k_pol_trunk, dim3((unsigned)((s.A + kTileRows - 1) / kTileRows)), dim3(kTrunkThreads), kTrunkLds,
-                       st, s, p, L, useList, logits, actions);
+    hipLaunchKernelGGL(k_pol_trunk, dim3((unsigned)((rows + kTileRows - 1) / kTileRows)), dim3(kTrunkThreads), kTrunkLds,
+                       st, s, p, L, fwdSlot, logits, actions);
     return check(hipGetLastError());
 }
 
@@ -515,16 +628,20 @@ int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int pa
 {
     hipStream_t st = (hipStream_t)stream;
     if (parts & kPolicySelect) {
-        if (check(hipMemsetAsync(p.count, 0, sizeof(int32_t), st))) return -1;
-        hipLaunchKernelGGL(k_pol_select, dim3((unsigned)((s.A + 255) / 256)), dim3(256), 0, st, s, p.list, p.count);
+        const dim3 grid((unsigned)((s.A + kSelThreads - 1) / kSelThreads));
+        if (check(hipMemsetAsync(p.count, 0, kSlots * sizeof(int32_t), st))) return -1;
+        hipLaunchKernelGGL(k_pol_count, grid, dim3(kSelThreads), 0, st, s, p);
+        hipLaunchKernelGGL(k_pol_plan, dim3(1), dim3(64), 0, st, p, (int)listTiles(s.A));
+        hipLaunchKernelGGL(k_pol_scatter, grid, dim3(kSelThreads), 0, st, s, p);
         if (check(hipGetLastError())) return -1;
     }
-    return run(s, p, 1, nullptr, nullptr, st, parts);
+    return run(s, p, -1, nullptr, nullptr, st, parts);
 }
 
-int launchPolicyForward(const DevState &s, const PolicyDev &p, float *logits, int32_t *actions, void *stream)
+int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream)
 {
-    return run(s, p, 0, logits, actions, (hipStream_t)stream);
+    if (slot < 0 || slot >= kSlots || !((p.mask >> slot) & 1u)) return -1;
+    return run(s, p, slot, logits, actions, (hipStream_t)stream);
 }
 
 // wPacked: pol::packB of w with N padded to a multiple of 64 columns

@@ -221,8 +221,14 @@ PYBIND11_MODULE(madrona_mp_env, m)
                      py::gil_scoped_release nogil;
                      check(mpenv_create(&cfg, &h->mgr));
                  }
-                 // Manager::Config::policyWeightsPath (mgr.hpp:49): loaded after the create, failing loudly
-                 if (!policy_weights_path.is_none()) {
+                 // Manager::Config::policyWeightsPath (mgr.hpp:49): loaded after the create, failing loudly;
+                 // a {policy_id: dir} dict loads one checkpoint per id (mpenv_policy_slots.h)
+                 if (py::isinstance<py::dict>(policy_weights_path)) {
+                     for (auto item : policy_weights_path.cast<py::dict>()) {
+                         weights = py::str(item.second);
+                         check(mpenv_policy_load_slot(h->mgr, item.first.cast<int32_t>(), weights.c_str()));
+                     }
+                 } else if (!policy_weights_path.is_none()) {
                      weights = py::str(policy_weights_path);
                      check(mpenv_policy_load(h->mgr, weights.c_str()));
                  }
@@ -283,19 +289,32 @@ PYBIND11_MODULE(madrona_mp_env, m)
         }, py::arg("out"), py::arg("stream"))
         // in-sim policy inference (include/mpenv.h mpenv_policy_*): logits
         // [A][37] f32 and actions [A][6] i32 are device pointers as integers
-        .def("load_policy", [](PySimManager &s, const std::string &dir) {
-            check(mpenv_policy_load(s.h->mgr, dir.c_str()));
-        }, py::arg("dir"))
-        .def("unload_policy", [](PySimManager &s) { check(mpenv_policy_unload(s.h->mgr)); })
+        // policy_id: the checkpoint slot (mpenv_policy_slots.h); unload_policy() empties every slot
+        .def("load_policy", [](PySimManager &s, const std::string &dir, int32_t policy_id) {
+            check(mpenv_policy_load_slot(s.h->mgr, policy_id, dir.c_str()));
+        }, py::arg("dir"), py::arg("policy_id") = 0)
+        .def("unload_policy", [](PySimManager &s, py::object policy_id) {
+            check(policy_id.is_none() ? mpenv_policy_unload(s.h->mgr)
+                                      : mpenv_policy_unload_slot(s.h->mgr, policy_id.cast<int32_t>()));
+        }, py::arg("policy_id") = py::none())
+        .def("policy_slots", [](PySimManager &s) {
+            uint32_t mask = 0;
+            check(mpenv_policy_slots(s.h->mgr, &mask));
+            std::vector<int> ids;
+            for (int i = 0; i < MPENV_POLICY_SLOTS; i++)
+                if ((mask >> i) & 1u) ids.push_back(i);
+            return ids;
+        })
         .def("policy_loaded", [](PySimManager &s) {
             int32_t on = 0;
             check(mpenv_policy_loaded(s.h->mgr, &on));
             return on != 0;
         })
-        .def("policy_forward", [](PySimManager &s, uintptr_t logits, uintptr_t actions, uintptr_t stream) {
-            check(mpenv_policy_forward(s.h->mgr, reinterpret_cast<float *>(logits), reinterpret_cast<int32_t *>(actions),
-                                       reinterpret_cast<void *>(stream)));
-        }, py::arg("logits"), py::arg("actions") = 0, py::arg("stream") = 0)
+        .def("policy_forward", [](PySimManager &s, uintptr_t logits, uintptr_t actions, uintptr_t stream,
+                                  int32_t policy_id) {
+            check(mpenv_policy_forward_slot(s.h->mgr, policy_id, reinterpret_cast<float *>(logits),
+                                            reinterpret_cast<int32_t *>(actions), reinterpret_cast<void *>(stream)));
+        }, py::arg("logits"), py::arg("actions") = 0, py::arg("stream") = 0, py::arg("policy_id") = 0)
         // world checkpoints (include/mpenv.h mpenv_state_*): device pointers
         // as integers, 0 = no world map / the manager's own stream
         .def("state_bytes", [](PySimManager &s) {

@@ -12,7 +12,12 @@ f32-input MFMA; trunk_tflops counts the trunk's and heads' 739,840
 multiply-adds per agent over the trunk kernel's time.  The checkpoint is the
 random one of tests/policy_testlib.py (the time does not depend on the values).
 
-usage: python tools/policy_timing.py [--out profiles/policy_timing.json]"""
+--slots N (league play, mpenv_policy_slots.h): N synthetic checkpoints in
+slots 0 .. N-1 and the policy agents dealt over them evenly, agent by agent;
+mpenv_policy_forward stays slot 0 for every agent.  --batches picks C3, C2 or
+both.
+
+usage: python tools/policy_timing.py [--slots N] [--batches C3,C2] [--out profiles/policy_timing.json]"""
 import argparse
 import ctypes as C
 import json
@@ -26,6 +31,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mpenv_testlib as T  # noqa: E402
+import policy_slots_abi  # noqa: E402
 import policy_testlib as P  # noqa: E402
 
 REPS, ROUNDS = 3, 5
@@ -35,7 +41,7 @@ PEAK_TFLOPS = 155.0
 SELECT, EMBED, TRUNK, ALL = 1, 2, 4, 7
 
 
-def measure(ts, W, ckpt):
+def measure(ts, W, ckpts):
     A = W * 2 * ts
     lib = T.lib_mpenv()
     e = T.Engine(W, ts)
@@ -62,12 +68,20 @@ def measure(ts, W, ckpt):
     for s in range(20):
         e.combat_actions(ring + (s % 4) * A * 24, None, 1)
         e.step()
-    ok(lib.mpenv_policy_load(e.h, ckpt.encode()))
+    if len(ckpts) == 1:
+        ok(lib.mpenv_policy_load(e.h, ckpts[0].encode()))
+    else:
+        policy_slots_abi.bind(lib)
+        for slot, ckpt in enumerate(ckpts):
+            ok(lib.mpenv_policy_load_slot(e.h, slot, ckpt.encode()))
 
     rng = np.random.default_rng(3)
     team0 = (np.arange(A) % (2 * ts)) < ts
     ids = {"100pct": np.zeros(A, np.int32), "50pct_one_team": np.where(team0, 0, -2).astype(np.int32),
            "10pct": np.where(rng.uniform(0, 1, A) < 0.1, 0, -2).astype(np.int32)}
+    for v in ids.values():  # the k-th policy agent on checkpoint k mod N
+        on = np.flatnonzero(v >= 0)
+        v[on] = np.arange(len(on)) % len(ckpts)
     logits = e.mem.upload(np.zeros((A, P.LOGITS), np.float32))
     variants = [(f"step_policy_{k}", k, ALL) for k in ids]
     variants += [("select_embed_100pct", "100pct", SELECT | EMBED), ("trunk_100pct", "100pct", TRUNK),
@@ -91,6 +105,7 @@ def measure(ts, W, ckpt):
                 times[name].append(ms.value / REPS)
     floor_ms = A * MACS_TOTAL * 2 / (PEAK_TFLOPS * 1e12) * 1e3
     out = {"workload": f"{ts}v{ts} x {W} worlds ({A} agents) after 20 seek-and-fight steps",
+           "checkpoint_slots": len(ckpts),
            "floor_ms_all_agents": round(floor_ms, 4), "reps_per_round": REPS, "rounds": ROUNDS, "calls": {}}
     for name, which, _ in variants:
         ms = statistics.median(times[name])
@@ -111,11 +126,17 @@ def measure(ts, W, ckpt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "policy_timing.json"))
+    ap.add_argument("--slots", type=int, default=1, help="checkpoints, in slots 0 .. N-1 (1 to 32)")
+    ap.add_argument("--batches", default="C3,C2")
     args = ap.parse_args()
+    if not 1 <= args.slots <= policy_slots_abi.POLICY_SLOTS:
+        ap.error("--slots must be in [1, 32]")
+    shapes = {"C3": (6, 16384), "C2": (3, 4096)}
     with tempfile.TemporaryDirectory() as d:
-        ckpt = os.path.join(d, "ckpt")
-        P.write_checkpoint(ckpt, 21)
-        out = {"C3": measure(6, 16384, ckpt), "C2": measure(3, 4096, ckpt)}
+        ckpts = [os.path.join(d, f"ckpt{k}") for k in range(args.slots)]
+        for k, ckpt in enumerate(ckpts):
+            P.write_checkpoint(ckpt, 21 + k)
+        out = {b: measure(*shapes[b], ckpts) for b in args.batches.split(",")}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
