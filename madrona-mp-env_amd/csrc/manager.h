@@ -1,0 +1,302 @@
+// manager.h — what manager.cpp and manager_scene.cpp share, and nothing else
+// includes: the error channel of the C ABI, the owning HIP handle types and
+// struct mpenv_manager.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+#include "engine.h"
+#include "mpenv.h"
+#include "policy.h"
+#include "scene.h"
+
+using namespace mpenv;
+
+namespace mpenv {
+// Sets this thread's mpenv_last_error text and returns `code` (manager.cpp).
+int fail(int code, const std::string &msg);
+// manager_scene.cpp: the scene's device image (m.sc and its buffers) from
+// m.scene and m.cfg.
+void buildSceneDev(mpenv_manager &m);
+} // namespace mpenv
+
+#define HIP_CHECK(expr)                                                                   \
+    do {                                                                                  \
+        hipError_t e_ = (expr);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e_) + \
+                                     " at " #expr);                                       \
+        }                                                                                 \
+    } while (0)
+
+// The result of a launchX() of engine.h: non-zero is a failed launch.
+inline void launched(int rc, const char *what)
+{
+    if (rc) throw std::runtime_error(what);
+}
+
+// The body of a C ABI entry point: its return code (MPENV_OK for a body
+// that returns nothing), or the code of what it threw -- MPENV_ERR_IO for an
+// IoError (scene.h), `other` for any other exception -- with the exception's
+// text as mpenv_last_error.
+template <class F>
+int guarded(F &&body, int other = MPENV_ERR_HIP)
+{
+    try {
+        if constexpr (std::is_void<decltype(body())>::value) {
+            body();
+            return MPENV_OK;
+        } else {
+            return body();
+        }
+    } catch (const IoError &e) {
+        return fail(MPENV_ERR_IO, e.what());
+    } catch (const std::exception &e) {
+        return fail(other, e.what());
+    }
+}
+
+// One owned HIP handle, released with Drop by the destructor; move-only,
+// empty (null) by default and after being moved from into a new Handle.
+// Move assignment swaps: the source leaves with the target's previous
+// handle and releases it when it dies (every source here is a temporary or
+// a local at the end of its scope).  put() is where a HIP create call
+// writes the handle: on an empty one only.
+template <class T, auto Drop>
+class Handle {
+public:
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h_(o.release()) {}
+    Handle &operator=(Handle &&o) noexcept { std::swap(h_, o.h_); return *this; }
+    ~Handle() { if (h_) (void)Drop(h_); }
+    T get() const { return h_; }
+    operator T() const { return h_; }
+    T *put() { return &h_; }
+    T release() { return std::exchange(h_, T {}); } // the caller owns it from here
+
+private:
+    T h_ {};
+};
+
+inline hipError_t syncAndDestroy(hipStream_t s)
+{
+    (void)hipStreamSynchronize(s);
+    return hipStreamDestroy(s);
+}
+
+struct Stream : Handle<hipStream_t, syncAndDestroy> {
+    static Stream create(unsigned flags)
+    {
+        Stream s;
+        HIP_CHECK(hipStreamCreateWithFlags(s.put(), flags));
+        return s;
+    }
+};
+
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    static Event create(unsigned flags)
+    {
+        Event e;
+        HIP_CHECK(hipEventCreateWithFlags(e.put(), flags));
+        return e;
+    }
+};
+
+struct DevPtr : Handle<void *, hipFree> {
+    static DevPtr create(size_t bytes)
+    {
+        DevPtr p;
+        HIP_CHECK(hipMalloc(p.put(), bytes));
+        return p;
+    }
+};
+
+// A captured graph and its executable; the executable is destroyed first.
+using Graph = Handle<hipGraph_t, hipGraphDestroy>;
+struct StepGraph {
+    Graph graph;
+    Handle<hipGraphExec_t, hipGraphExecDestroy> exec;
+};
+
+// A stream beside a main one.  Its work starts after an event the caller
+// recorded on the main stream (one fork event may start several side
+// streams) and is joined back through `done`.  Both handles or neither.
+struct SideStream {
+    Stream stream;
+    Event done;
+    static SideStream create()
+    {
+        return { Stream::create(hipStreamNonBlocking), Event::create(hipEventDisableTiming) };
+    }
+    explicit operator bool() const { return stream != nullptr; }
+    void startAfter(hipEvent_t recorded) const { HIP_CHECK(hipStreamWaitEvent(stream, recorded, 0)); }
+    void markDone() const { HIP_CHECK(hipEventRecord(done, stream)); }
+    void joinInto(hipStream_t st) const { HIP_CHECK(hipStreamWaitEvent(st, done, 0)); }
+};
+
+struct TensorDesc {
+    void *ptr = nullptr;
+    int32_t dtype = MPENV_DTYPE_FLOAT32;
+    std::vector<int64_t> dims;
+    size_t bytes() const
+    {
+        size_t n = 4;
+        for (int64_t d : dims) n *= (size_t)d;
+        return n;
+    }
+};
+
+// Handle members are released in reverse order of declaration: the step
+// graph's executable before every stream, the main stream last.
+struct mpenv_manager {
+    mpenv_config cfg;
+    std::string scenePath;
+    int gpu = 0;
+    Scene scene;
+    SceneDev sc;
+    DevState S;
+    Stream stream;
+    std::vector<void *> allocations;
+
+    // Debug gather buffers (allocated lazily)
+    float *dbgAF = nullptr, *dbgWF = nullptr, *dbgCrumbs = nullptr;
+    int32_t *dbgAI = nullptr, *dbgWI = nullptr;
+    uint32_t *dbgExplore = nullptr;
+
+    // World groups: contiguous world ranges stepped on their own streams
+    // (fork/join with events) so independent kernels overlap on the GPU.
+    // One fork event starts every group; group 0 runs on the caller's
+    // stream, so gside[0] is made (as it always was) and never used.
+    int groups = 1;
+    std::vector<SideStream> gside;
+    std::vector<DevState> gS;
+    std::vector<SceneDev> gsc;
+    Event forkEv;
+    // One group only: k_lidar on a branch stream beside k_vis -> k_obs (no
+    // data dependence between them after k_sim).  MPENV_LIDAR_BRANCH=1.
+    bool lidarBranch = false;
+    SideStream bSide;
+    Event bForkEv;
+    // k_lidar's tasks per wave: 0 = lidarItersFor(agents of the range), else
+    // forced (mpenv_set_lidar_iters)
+    int lidarIters = 0;
+    int lidarItersOf(const DevState &R) const { return lidarIters ? lidarIters : lidarItersFor(R.A); }
+    // gpuStreamStep: the agent maps' zero fills (no dependence on the step)
+    // on a side stream of their own, overlapping the step's kernels; joined
+    // back into the caller's stream before the call returns.
+    SideStream zSide;
+    Event zForkEv;
+
+    // Record / replay / event logs (mgr.cpp:155-300: per-step file I/O
+    // around the Step graph)
+    FILE *replayFile = nullptr, *recordFile = nullptr, *eventsFile = nullptr, *stepsFile = nullptr;
+    bool replayEof = false;
+    std::vector<mpenv_step_log> hostLog;
+    std::vector<mpenv_game_event> hostEvents;
+    std::vector<mpenv_packed_step_snapshot> hostSnaps;
+    std::vector<int32_t> hostSnapWritten;
+
+    // Workload counters (DevState::stats, kNumStats u64), allocated on first use
+    unsigned long long *statsBuf = nullptr;
+
+    // Kernel timing
+    bool timing = false;
+    std::vector<Event> eventPool;
+    size_t eventsUsed = 0;
+
+    // The Step graph as a captured HIP graph (all world groups, fork/join
+    // included), replayed with one hipGraphLaunch per step.  Kernel
+    // arguments are captured by value, so the graph is keyed on the bytes of
+    // every argument struct and re-captured when any of them changes (world
+    // groups, stats buffer, ...).  MPENV_STEP_GRAPH=0 launches kernel by
+    // kernel instead; timed steps (events between kernels) always do.
+    bool useGraph = true;
+    Stream capStream;
+    StepGraph step;
+    std::vector<char> graphKey;
+    // recorded after every hipGraphLaunch on the launch's stream: a
+    // re-capture waits on it before destroying the previous exec (its last
+    // launch may still run on a caller stream the manager does not own)
+    Event graphDoneEv;
+    int64_t graphCaptures = 0; // mpenv_graph_captures
+    std::string graphOffReason; // why the step is not replayed from a graph (mpenv_graph_status)
+    uint32_t *wireErr = nullptr; // device word raised by a rejected wire message (wire.hip)
+    int32_t *wireEp = nullptr;   // [2][W] a shadow's episode counters of the last two messages
+    int wireParity = 0;          // which half of wireEp holds the previous message's
+    OutTab *outTabDev = nullptr; // gpuStreamStep's caller output buffers (engine.h OutTab)
+    // World checkpoints (state.hip): the descriptor table, its device copy,
+    // and which log mode (append-only files) rules them out for this manager
+    StateTab stateTab;
+    StateTab *stateTabDev = nullptr;
+    const char *stateRefused = nullptr;
+    // In-sim policy inference (policy.hip; DESIGN.md §2 definition 15): the
+    // one parameter blob per occupied checkpoint slot (polBlobs, the host's
+    // copy of the device table polDev.blobs; polDev.mask says which); the
+    // table and the work buffers live from the first load to the last
+    // unload; while any slot is occupied (polLoaded), every step first
+    // writes the served agents' actions
+    PolicyDev polDev {};
+    const float *polBlobs[pol::kSlots] = {};
+    int32_t *polTab = nullptr; // the allocation behind polDev's counters and tile tables
+    bool polLoaded = false;
+    // the last step was a gpuStreamStep that wrote the observation rows into
+    // its caller's buffers only (OutTab): the engine's own rows, which the
+    // policy, the aim-bot (mpenv_combat_actions) and a snapshot
+    // (mpenv_state_save) read, are behind until a plain step, a copying
+    // gpuStreamStep or an init writes them again; those three calls are
+    // refused meanwhile (staleExports)
+    bool exportsStale = false;
+
+    ~mpenv_manager();
+
+    template <typename T>
+    T *alloc(size_t count)
+    {
+        size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+        void *p = nullptr;
+        HIP_CHECK(hipMalloc(&p, bytes));
+        HIP_CHECK(hipMemsetAsync(p, 0, bytes, stream));
+        allocations.push_back(p);
+        return static_cast<T *>(p);
+    }
+
+    // Host->device copy ordered on the manager stream (after the zeroing
+    // memsets issued by alloc() and any in-flight step), then waited for.
+    void upload(void *dst, const void *src, size_t bytes)
+    {
+        HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+    }
+
+    void freePolicy();
+    void allocPolicyWork();
+    void setPolicySlot(int slot, const float *blob);
+    void record(hipStream_t st);
+    void stepRange(const DevState &R, const SceneDev &rsc, hipStream_t st);
+    void preStep(hipStream_t st);
+    void postStep(hipStream_t st);
+    void runStep(hipStream_t st);
+    std::vector<char> argKey() const;
+    void launchStep(hipStream_t st);
+    bool captureStep();
+    void launchStepDirect(hipStream_t st);
+    void setupGroups(int want);
+    void runInitGraph(hipStream_t st);
+    bool exportDesc(int32_t id, TensorDesc &d);
+    void *exportPtr(int32_t id);
+    void gatherDebug(bool explore = false);
+};
+
+// The caller's stream of an entry point, or the manager's own for null.
+inline hipStream_t streamOf(const mpenv_manager *m, void *stream)
+{
+    return stream ? (hipStream_t)stream : (hipStream_t)m->stream;
+}

@@ -26,7 +26,7 @@ void readPod(std::ifstream &f, T *dst, size_t n, const std::string &path)
 {
     f.read(reinterpret_cast<char *>(dst), (std::streamsize)(sizeof(T) * n));
     if (!f) {
-        throw std::runtime_error("mpenv: truncated file " + path);
+        throw IoError("mpenv: truncated file " + path);
     }
 }
 
@@ -34,7 +34,7 @@ std::ifstream openOrThrow(const std::string &path)
 {
     std::ifstream f(path, std::ios::binary);
     if (!f.is_open()) {
-        throw std::runtime_error("mpenv: failed to open " + path);
+        throw IoError("mpenv: failed to open " + path);
     }
     return f;
 }
@@ -611,16 +611,16 @@ Scene loadScene(const std::string &dir, bool spawn_in_middle)
             const uint64_t voff = mesh_info[4 * m + 0], nv = mesh_info[4 * m + 1];
             const uint64_t toff = mesh_info[4 * m + 2], nt = mesh_info[4 * m + 3];
             if (voff + nv > total_verts || toff + nt > total_tris)
-                throw std::runtime_error(path + ": mesh " + std::to_string(m) +
-                                         " range outside the vertex/triangle arrays (truncated or malformed file)");
+                throw IoError(path + ": mesh " + std::to_string(m) +
+                              " range outside the vertex/triangle arrays (truncated or malformed file)");
             for (uint64_t i = 0; i < nt; i++) {
                 uint32_t mat = tri_mats[toff + i];
                 if (mat < mat_flags.size() && mat_flags[mat] == 1u) continue;
                 for (int k = 0; k < 3; k++) {
                     const uint64_t vi = idx[3 * (toff + i) + k];
                     if (vi >= nv)
-                        throw std::runtime_error(path + ": mesh " + std::to_string(m) +
-                                                 " vertex index out of range (truncated or malformed file)");
+                        throw IoError(path + ": mesh " + std::to_string(m) +
+                                      " vertex index out of range (truncated or malformed file)");
                     s.triVerts.push_back(verts[voff + vi]);
                 }
             }

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <string>
 #include <map>
+#include <stdexcept>
 #include <vector>
 
 #include "mpenv_core.h"
@@ -106,9 +107,14 @@ struct Scene {
     NavMesh nav;
 };
 
+// A file that cannot be opened or ends early: MPENV_ERR_IO at the C ABI.
+struct IoError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
 // Loads <dir>/{collisions,navmesh,spawns,zones}.bin (bindings.cpp:56-81) and
-// builds the BVH.  Throws std::runtime_error on I/O failure (the reference
-// FATALs, map_importer.cpp:229-231).
+// builds the BVH.  Throws IoError on I/O failure (the reference FATALs,
+// map_importer.cpp:229-231).
 Scene loadScene(const std::string &scene_dir, bool spawn_in_middle = false);
 
 // Dedups, triangulates and links the navmesh and builds/reads its A* table.

@@ -3,6 +3,8 @@ Python module surface (src/bindings.cpp:11-160) and loud failure modes."""
 import ctypes as C
 import os
 import re
+import shutil
+import struct
 import subprocess
 
 import pytest
@@ -118,6 +120,58 @@ def test_create_rejects_unsupported_configs(kw, needle):
     assert rc != 0 and not h.value
     msg = lib.mpenv_last_error().decode()
     assert needle.lower() in msg.lower(), msg
+
+
+@pytest.mark.gpu
+def test_create_error_codes(tmp_path):
+    """What mpenv_create returns once a device is there (without one it stops
+    at "no HIP device available"): a scene or curriculum file that cannot be
+    opened or a collisions.bin with a mesh range past its arrays is
+    MPENV_ERR_IO, a scene the task cannot use MPENV_ERR_HIP."""
+    lib = T.lib_mpenv()
+
+    def create(**kw):
+        h = C.c_void_p()
+        rc = lib.mpenv_create(C.byref(_cfg(**kw)), C.byref(h))
+        assert not h.value
+        return rc, lib.mpenv_last_error().decode()
+
+    rc, msg = create(scene_path=str(tmp_path / "no_such_scene").encode())
+    assert rc == -2 and "open" in msg, (rc, msg)  # MPENV_ERR_IO
+    rc, msg = create(curriculum_data_path=str(tmp_path / "no_such_file").encode())
+    assert rc == -2 and "open" in msg, (rc, msg)
+    rc, msg = create(task_type=T.TASK_ZONE_CAPTURE_DEFEND)  # simple_map has three zones
+    assert rc == -3 and ">= 4 zones" in msg, (rc, msg)  # MPENV_ERR_HIP
+    # a collisions.bin whose last mesh claims more triangles than the file holds: the file's last
+    # 16 bytes are that mesh's (vertexOffset, numVertices, triOffset, numTris)
+    bad = tmp_path / "bad_mesh_range"
+    bad.mkdir()
+    for f in ("collisions.bin", "navmesh.bin", "spawns.bin", "zones.bin"):
+        shutil.copy(os.path.join(T.SCENE, f), bad)
+    raw = bytearray((bad / "collisions.bin").read_bytes())
+    raw[-4:] = struct.pack("<I", 0x7FFFFFFF)
+    (bad / "collisions.bin").write_bytes(bytes(raw))
+    rc, msg = create(scene_path=str(bad).encode())
+    assert rc == -2 and "range outside" in msg and "truncated or malformed" in msg, (rc, msg)
+
+
+def test_every_manager_call_refuses_a_null_handle():
+    """Each function that takes the manager handle first and returns a code,
+    called with a null handle and zero or null for the rest."""
+    from mpenv_abi import SIGNATURES
+
+    lib = T.lib_mpenv()
+    calls = [n for n, (ret, args) in SIGNATURES.items() if ret is C.c_int32 and args and args[0] is C.c_void_p]
+    assert len(calls) >= 44  # the selection finds them
+    for name in calls:
+        args = [None if a is C.c_void_p or a is C.c_char_p or issubclass(a, C._Pointer) else 0
+                for a in SIGNATURES[name][1]]
+        # the error text is per thread and stays: put a known other one there first
+        assert lib.mpenv_scene_quirk_grid(None, None, None, None) == -1
+        assert lib.mpenv_last_error() == b"num_words is null"
+        assert getattr(lib, name)(*args) == -1, name  # MPENV_ERR_INVALID
+        msg = lib.mpenv_last_error().decode()
+        assert msg != "num_words is null" and ("null" in msg or "argument" in msg), (name, msg)
 
 
 def test_python_module_surface():
