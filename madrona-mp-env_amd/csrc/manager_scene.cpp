@@ -66,8 +66,10 @@ void mpenv::buildSceneDev(mpenv_manager &m)
     BVHNode *d_nodes = m.alloc<BVHNode>(s.nodes.size());
     m.upload(d_nodes, s.nodes.data(), sizeof(BVHNode) * s.nodes.size());
     {
-        // k_lidar: octant images of the lidar tree and its triangles
-        const std::vector<BVHNode> oct = octantNodeImages(s.lidarNodes);
+        // k_lidar: octant images of the lidar tree, each without the
+        // triangles its octant's rays can only meet from behind, and the
+        // tree's triangles
+        const std::vector<BVHNode> oct = octantNodeImages(s.lidarNodes, s.lidarVerts, true);
         BVHNode *d_oct = m.alloc<BVHNode>(oct.size());
         m.upload(d_oct, oct.data(), sizeof(BVHNode) * oct.size());
         sc.octNodes = d_oct;

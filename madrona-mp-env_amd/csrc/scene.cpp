@@ -432,12 +432,62 @@ void buildBVH(const std::vector<Vec3> &tri_verts, Scene &out, const BVHBuildOpts
     out.maxStackAnyOrder = std::max(1, occ_any[0]);
 }
 
-std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes)
+bool octantBackFacing(const Vec3 &a, const Vec3 &b, const Vec3 &c, int oct)
+{
+    const double e1[3] = { (double)b.x - a.x, (double)b.y - a.y, (double)b.z - a.z };
+    const double e2[3] = { (double)c.x - a.x, (double)c.y - a.y, (double)c.z - a.z };
+    const double nrm[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                            e1[0] * e2[1] - e1[1] * e2[0] };
+    const double len = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+    if (!(len > 0.0)) return false; // degenerate: the float test decides
+    for (int i = 0; i < 3; i++) {
+        const double s = (oct >> i) & 1 ? -1.0 : 1.0;
+        if (s * nrm[i] < 0.0) return false;
+        // a component the vertices' rounding could have given either sign
+        if (nrm[i] != 0.0 && std::fabs(nrm[i]) < 1e-6 * len) return false;
+    }
+    return true;
+}
+
+std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes, const std::vector<Vec3> &verts, bool prune)
 {
     const size_t n = nodes.size();
     std::vector<BVHNode> out(8 * n);
     for (int oct = 0; oct < 8; oct++) {
         const double sgn[3] = { (oct & 1) ? -1.0 : 1.0, (oct & 2) ? -1.0 : 1.0, (oct & 4) ? -1.0 : 1.0 };
+        // prune: this octant's copy of every slot's child / triangle count
+        // with the back-facing triangles taken out (octantBackFacing), -1
+        // for a leaf or a subtree with no survivor.  Children have larger
+        // ids than their parent (DFS pre-order), so one descending pass
+        // sees every subtree before its parent.
+        std::vector<int32_t> kid(4 * n);
+        std::vector<uint8_t> cnt(4 * n);
+        for (size_t ni = n; ni-- > 0;) {
+            const BVHNode &nd = nodes[ni];
+            for (int i = 0; i < 4; i++) {
+                int32_t c = nd.children[i];
+                uint8_t k = nd.triSize[i];
+                if (prune && c != -1 && (c & 0x80000000) && k > 0) {
+                    const int leaf = c & 0x7fffffff;
+                    if (k > 2 || (size_t)(leaf + k) * 3 > verts.size())
+                        throw std::runtime_error("mpenv: lidar leaf outside its vertex array");
+                    bool dead[2] = { false, false };
+                    for (int t = 0; t < k; t++)
+                        dead[t] = octantBackFacing(verts[(leaf + t) * 3], verts[(leaf + t) * 3 + 1],
+                                                   verts[(leaf + t) * 3 + 2], oct);
+                    if (dead[0] && (k == 1 || dead[1])) c = -1, k = 0;
+                    else if (dead[0]) c = (int32_t)(0x80000000u | (uint32_t)(leaf + 1)), k = 1;
+                    else if (k == 2 && dead[1]) k = 1;
+                } else if (prune && c != -1 && !(c & 0x80000000)) {
+                    if ((size_t)c <= ni || (size_t)c >= n) throw std::runtime_error("mpenv: lidar tree not in pre-order");
+                    bool live = false;
+                    for (int j = 0; j < 4; j++) live = live || kid[4 * c + j] != -1;
+                    if (!live) c = -1;
+                }
+                kid[4 * ni + i] = c;
+                cnt[4 * ni + i] = k;
+            }
+        }
         for (size_t ni = 0; ni < n; ni++) {
             const BVHNode &nd = nodes[ni];
             const int8_t ex[3] = { nd.expX, nd.expY, nd.expZ };
@@ -452,8 +502,8 @@ std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes)
             }
             std::vector<int> leaves, inner, empty;
             for (int i = 0; i < 4; i++) {
-                if (nd.children[i] == -1) empty.push_back(i);
-                else if (nd.children[i] & 0x80000000) leaves.push_back(i);
+                if (kid[4 * ni + i] == -1) empty.push_back(i);
+                else if (kid[4 * ni + i] & 0x80000000) leaves.push_back(i);
                 else inner.push_back(i);
             }
             std::stable_sort(leaves.begin(), leaves.end(), [&](int a, int b) { return key[a] < key[b]; });
@@ -464,10 +514,10 @@ std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes)
             BVHNode p = nd;
             for (int k = 0; k < 4; k++) {
                 const int i = ord[k];
-                p.triSize[k] = nd.triSize[i];
+                p.triSize[k] = cnt[4 * ni + i];
                 p.qMinX[k] = nd.qMinX[i]; p.qMinY[k] = nd.qMinY[i]; p.qMinZ[k] = nd.qMinZ[i];
                 p.qMaxX[k] = nd.qMaxX[i]; p.qMaxY[k] = nd.qMaxY[i]; p.qMaxZ[k] = nd.qMaxZ[i];
-                p.children[k] = nd.children[i];
+                p.children[k] = kid[4 * ni + i];
                 // near slab first for this octant's direction signs
                 if (oct & 1) std::swap(p.qMinX[k], p.qMaxX[k]);
                 if (oct & 2) std::swap(p.qMinY[k], p.qMaxY[k]);

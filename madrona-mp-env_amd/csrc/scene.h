@@ -177,7 +177,29 @@ void buildBVH(const std::vector<mp::Vec3> &tri_verts, Scene &out, const BVHBuild
 // (mesh_bvh.inl:165-183 takes the min / max of the two; the slab t is
 // monotonic in q with the slope's sign, so the values are the same).
 // Node indices, unquantised bounds and leaves are unchanged.
-std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes);
+//
+// prune (verts: the tree's leaf-order vertices, 3 per triangle): copy o also
+// drops the triangles that are back-facing for every direction of octant o
+// (octantBackFacing below; DESIGN.md §2 definition 16).  A leaf slot whose
+// first triangle is dropped points at its second one with triSize 1, one
+// whose second is dropped keeps its child with triSize 1, one that loses
+// both becomes empty (-1, triSize 0), and so does an internal child whose
+// subtree keeps no triangle.  Surviving slots keep their box bytes and their
+// relative order, so a ray of octant o meets the same boxes and triangles
+// in the same order minus tests that could not have accepted a hit; the
+// emptied slots join the empty ones at the tail.  Node numbering, the node
+// count and the header bytes (internalNodes included) stay those of the
+// full tree.
+std::vector<BVHNode> octantNodeImages(const std::vector<BVHNode> &nodes, const std::vector<mp::Vec3> &verts = {},
+                                      bool prune = false);
+
+// True when triangle (a, b, c) cannot be hit by any ray whose direction sign
+// bits are `oct`: rayTri culls back faces (U, V, W < 0 rejects), and with
+// n = (b - a) x (c - a) in double, s_i n_i >= 0 on every axis (s_i = -1
+// where bit i is set) gives n . d >= 0 for all such d.  A zero normal, or a
+// component that is non-zero yet below 1e-6 |n| (its sign may be rounding of
+// the float vertices), answers false: such triangles stay in every image.
+bool octantBackFacing(const mp::Vec3 &a, const mp::Vec3 &b, const mp::Vec3 &c, int oct);
 
 // The sphere cast's vertex test (mesh_bvh.inl:1073-1104) subtracts a vertex
 // already taken relative to the origin o from o again, and returns t = 0

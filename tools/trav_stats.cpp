@@ -9,6 +9,10 @@
 //       temporal-hint model: PREV holds the same ray slots one step earlier
 //       (tools/dump_lidar_rays.py at step s - 1); each ray first tests the
 //       triangle its slot hit then and starts with t_max = that hit's t
+//   TRAV_BACKFACE=1 trav_stats SCENE_DIR RAYS.f32
+//       the shipped lidar tree, full against each octant's image without its
+//       back-facing triangles (scene.h octantNodeImages), slot-aware cost
+//       (backfaceMain)
 //   TRAV_SCHED=1 trav_stats SCENE_DIR RAYS.f32
 //       k_lidar's task scheduling on the shipped lidar tree: how long a block
 //       of 16 waves lives against its mean wave work, tasks dealt statically
@@ -47,14 +51,17 @@ struct Stats {
 static std::vector<Node> nodes;
 static std::vector<float> verts;
 
+static bool g_cullBack = false; // TRAV_BACKFACE: reject back faces as the product's rayTri does
+
 static bool tri(const float *v, const float *o, const float *d, float tmax, float &t)
 {
     // Moller-Trumbore (analysis only)
     float e1[3], e2[3], p[3], q[3], s[3];
     for (int k = 0; k < 3; k++) { e1[k] = v[3 + k] - v[k]; e2[k] = v[6 + k] - v[k]; s[k] = o[k] - v[k]; }
     p[0] = d[1] * e2[2] - d[2] * e2[1]; p[1] = d[2] * e2[0] - d[0] * e2[2]; p[2] = d[0] * e2[1] - d[1] * e2[0];
-    float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
+    float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2]; // = -n . d, n = e1 x e2
     if (std::fabs(det) < 1e-12f) return false;
+    if (g_cullBack && det < 0) return false;
     float inv = 1.f / det;
     float u = (s[0] * p[0] + s[1] * p[1] + s[2] * p[2]) * inv;
     if (u < 0 || u > 1) return false;
@@ -810,15 +817,45 @@ static int pairMain(const std::vector<float> &rays)
 struct KM {
     double waves = 0, nodeIters = 0, triIters = 0, pops = 0, tris = 0, wrong = 0;
     double triItersMerged = 0; // per iteration: the most triangle tests any lane runs over all its slots
+    double boxes = 0;          // box tests over all lanes
+    double boxIters = 0;       // per iteration: the slots whose box test any lane runs
+    // slot-aware cost (TRAV_BACKFACE; counted on the gfx950 ISA of the loop): 28 per node iteration + 3 per
+    // slot + 22 per box test run by any lane + 45 per triangle iteration
+    double slotCost() const { return (28.0 + 3.0 * 4) * nodeIters + 22.0 * boxIters + 45.0 * triIters; }
 };
 
 static bool g_deferTris = false; // TRAV_DEFER: every slot's box test at the node's entry t_max, then the triangles
 
 static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &vt, const std::vector<float> &rays,
                         bool fwd_waves, KM &km, const std::vector<float> *ref_t = nullptr, std::vector<float> *out_t = nullptr,
-                        std::vector<double> *wave_cost = nullptr) // [n / 64] weighted cost of each wave of this kind
+                        std::vector<double> *wave_cost = nullptr, // [n / 64] weighted cost of each wave of this kind
+                        const std::vector<uint8_t> *dead = nullptr) // [8][triangles]: emptied in place per octant
 {
     const size_t n = rays.size() / 6;
+    // per octant each slot's child and triangle count; with `dead` as
+    // scene.h octantNodeImages prunes them (children have larger ids)
+    std::vector<std::array<std::array<int32_t, 4>, 8>> kid(nd.size());
+    std::vector<std::array<std::array<int, 4>, 8>> cnt(nd.size());
+    const size_t ntri = vt.size() / 9;
+    for (int oct = 0; oct < 8; oct++)
+        for (size_t ni = nd.size(); ni-- > 0;)
+            for (int i = 0; i < 4; i++) {
+                int32_t c = nd[ni].children[i];
+                int k = nd[ni].triSize[i];
+                if (dead && c != -1 && (c & 0x80000000)) {
+                    const int leaf = c & 0x7fffffff;
+                    const bool d0 = k > 0 && (*dead)[oct * ntri + leaf], d1 = k > 1 && (*dead)[oct * ntri + leaf + 1];
+                    if (k > 0 && d0 && (k == 1 || d1)) c = -1, k = 0;
+                    else if (d0) c = (int32_t)(0x80000000u | (uint32_t)(leaf + 1)), k = 1;
+                    else if (d1) k = 1;
+                } else if (dead && c != -1) {
+                    bool live = false;
+                    for (int j = 0; j < 4; j++) live = live || kid[c][oct][j] != -1;
+                    if (!live) c = -1;
+                }
+                kid[ni][oct][i] = c;
+                cnt[ni][oct][i] = k;
+            }
     // octant slot orders
     std::vector<std::array<std::array<int, 4>, 8>> ord(nd.size());
     for (size_t ni = 0; ni < nd.size(); ni++) {
@@ -853,6 +890,7 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
         if (fwd != fwd_waves) continue;
         km.waves++;
         std::vector<std::vector<std::array<int, 4>>> lanes(64);
+        std::vector<std::vector<uint8_t>> boxm(64); // per iteration: the slots whose box this lane tested
         size_t mp = 0;
         for (int l = 0; l < 64; l++) {
             const float *o = &rays[6 * (w0 + l)], *d = o + 3;
@@ -866,6 +904,7 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
                 st.pop_back();
                 km.pops++;
                 lanes[l].push_back({ 0, 0, 0, 0 });
+                boxm[l].push_back(0);
                 const Node &x = nd[ni];
                 const float sx = std::ldexp(1.f, x.expX), sy = std::ldexp(1.f, x.expY), sz = std::ldexp(1.f, x.expZ);
                 const float tmax_entry = tmax;
@@ -873,7 +912,10 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
                 std::vector<int> dslot;
                 for (int k = 0; k < 4; k++) {
                     const int i = ord[ni][oct][k];
-                    if (x.children[i] == -1) continue;
+                    const int32_t child = kid[ni][oct][i];
+                    if (child == -1) continue;
+                    boxm[l].back() |= (uint8_t)(1 << k);
+                    km.boxes++;
                     const float lo[3] = { x.minX + sx * x.qMinX[i], x.minY + sy * x.qMinY[i], x.minZ + sz * x.qMinZ[i] };
                     const float hi[3] = { x.minX + sx * x.qMaxX[i], x.minY + sy * x.qMaxY[i], x.minZ + sz * x.qMaxZ[i] };
                     float tn = 0, tf = g_deferTris ? tmax_entry : tmax;
@@ -883,21 +925,21 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
                         tf = std::min(tf, std::max(p, q));
                     }
                     if (tn > tf) continue;
-                    if (x.children[i] & 0x80000000) {
-                        const int leaf = x.children[i] & 0x7fffffff;
+                    if (child & 0x80000000) {
+                        const int leaf = child & 0x7fffffff;
                         if (g_deferTris) {
-                            deferred.push_back({ leaf, x.triSize[i] });
+                            deferred.push_back({ leaf, cnt[ni][oct][i] });
                             dslot.push_back(k);
                             continue;
                         }
-                        for (int q = 0; q < x.triSize[i]; q++) {
+                        for (int q = 0; q < cnt[ni][oct][i]; q++) {
                             lanes[l].back()[k]++;
                             km.tris++;
                             float th;
                             if (tri(&vt[(leaf + q) * 9], o, d, tmax, th)) tmax = th;
                         }
                     } else {
-                        st.push_back(x.children[i]);
+                        st.push_back(child);
                     }
                 }
                 for (size_t e = 0; e < deferred.size(); e++)
@@ -928,9 +970,69 @@ static void kernelModel(const std::vector<Node> &nd, const std::vector<float> &v
             for (auto &L : lanes)
                 if (it < L.size()) mm = std::max(mm, L[it][0] + L[it][1] + L[it][2] + L[it][3]);
             km.triItersMerged += mm;
+            unsigned any = 0;
+            for (auto &M : boxm)
+                if (it < M.size()) any |= M[it];
+            km.boxIters += __builtin_popcount(any);
         }
         if (wave_cost) (*wave_cost)[w0 / 64] = 110.0 * mp + 45.0 * (km.triIters - triBefore);
     }
+}
+
+// ---- TRAV_BACKFACE: the shipped lidar tree with each octant's back-facing
+// triangles emptied in place (scene.h octantNodeImages' prune rule, restated
+// here in double on the float vertices), full against pruned under the
+// slot-aware cost.
+static int backfaceMain(const char *scene, const std::vector<float> &rays)
+{
+    int32_t nn = 0, nv = 0, ms = 0;
+    if (mpenv_scene_lidar_bvh(scene, nullptr, &nn, nullptr, &nv, &ms)) return 1;
+    std::vector<Node> nd(nn);
+    std::vector<float> vt((size_t)nv * 3);
+    mpenv_scene_lidar_bvh(scene, nd.data(), &nn, vt.data(), &nv, &ms);
+    const size_t ntri = vt.size() / 9;
+    std::vector<uint8_t> dead(8 * ntri, 0);
+    for (size_t t = 0; t < ntri; t++) {
+        const float *v = &vt[9 * t];
+        double e1[3], e2[3];
+        for (int k = 0; k < 3; k++) { e1[k] = (double)v[3 + k] - v[k]; e2[k] = (double)v[6 + k] - v[k]; }
+        const double nr[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
+        const double len = std::sqrt(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
+        for (int oct = 0; oct < 8 && len > 0; oct++) {
+            bool d = true;
+            for (int i = 0; i < 3; i++) {
+                const double s = (oct >> i) & 1 ? -1.0 : 1.0;
+                if (s * nr[i] < 0 || (nr[i] != 0 && std::fabs(nr[i]) < 1e-6 * len)) d = false;
+            }
+            dead[oct * ntri + t] = d;
+        }
+    }
+    for (int oct = 0; oct < 8; oct++) {
+        size_t k = 0;
+        for (size_t t = 0; t < ntri; t++) k += dead[oct * ntri + t];
+        printf("octant %d: %zu of %zu triangles back-facing\n", oct, k, ntri);
+    }
+    g_cullBack = true;
+    const size_t n = rays.size() / 6;
+    std::vector<float> t_full(n, 0.f), t_pruned(n, 0.f);
+    double base = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        KM f, r;
+        std::vector<float> &out = pass ? t_pruned : t_full;
+        kernelModel(nd, vt, rays, true, f, nullptr, &out, nullptr, pass ? &dead : nullptr);
+        kernelModel(nd, vt, rays, false, r, nullptr, &out, nullptr, pass ? &dead : nullptr);
+        const double unit = (f.slotCost() + r.slotCost()) / (f.waves / 4);
+        if (!pass) base = unit;
+        printf("%-7s fwd wave %6.0f rear wave %6.0f unit (4 fwd + 1 rear) %6.0f (%+.1f%%) | node it fwd %5.2f rear %5.2f | "
+               "box it fwd %5.2f rear %5.2f | tri it fwd %5.2f rear %5.2f | boxes/ray %.2f tris/ray %.2f\n",
+               pass ? "pruned" : "full", f.slotCost() / f.waves, r.slotCost() / r.waves, unit, 100.0 * (unit / base - 1),
+               f.nodeIters / f.waves, r.nodeIters / r.waves, f.boxIters / f.waves, r.boxIters / r.waves,
+               f.triIters / f.waves, r.triIters / r.waves, (f.boxes + r.boxes) / n, (f.tris + r.tris) / n);
+    }
+    size_t diff = 0;
+    for (size_t i = 0; i < n - n % 64; i++) diff += t_full[i] != t_pruned[i];
+    printf("rays whose closest hit differs between full and pruned: %zu of %zu\n", diff, n - n % 64);
+    return 0;
 }
 
 // ---- TRAV_SCHED: k_lidar's task loop.  A block of 16 waves owns iters x 16
@@ -1324,6 +1426,7 @@ int main(int argc, char **argv)
     size_t n = rays.size() / 6;
     g_deferTris = getenv("TRAV_DEFER") != nullptr;
     if (getenv("TRAV_TREES")) return treesMain(argv[1], rays);
+    if (getenv("TRAV_BACKFACE")) return backfaceMain(argv[1], rays);
     if (getenv("TRAV_SCHED")) return schedMain(argv[1], rays);
     {
         double un = 0, ut = 0;
