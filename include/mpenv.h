@@ -670,7 +670,11 @@ int mpenv_state_section_dtype(int32_t idx, int32_t *dtype);
  * alone, asynchronous on hip_stream -- it writes the policy agents' actions
  * and advances their RNG as a step would.  parts: bit 0 the selection, bit 1
  * the embed kernel, bit 2 the trunk kernel (7 = all; the trunk alone reuses
- * the selection and the embeddings of the last full call). */
+ * the selection and the embeddings of the last full call).
+ *
+ * Precision: mpenv_policy_precision.h, included below -- the trunk and the
+ * heads on the bf16 matrix cores for frozen opponents (MPENV_POLICY_BF16),
+ * where the default MPENV_POLICY_F32 is the bit-exact arithmetic above. */
 int mpenv_policy_check(const char *dir);
 int mpenv_policy_load(mpenv_manager *mgr, const char *dir);
 int mpenv_policy_unload(mpenv_manager *mgr);
@@ -683,6 +687,9 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
 /* the per-slot calls: mpenv_policy_load_slot, mpenv_policy_unload_slot,
  * mpenv_policy_slots, mpenv_policy_forward_slot */
 #include "mpenv_policy_slots.h"
+/* the precision switch: MPENV_POLICY_F32, MPENV_POLICY_BF16, mpenv_policy_set_precision,
+ * mpenv_policy_precision and the bf16 test hooks */
+#include "mpenv_policy_precision.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

@@ -212,6 +212,15 @@ public:
         return ids;
     }
     // logits [A][37] f32 and actions [A][6] i32 (or null) are device pointers;
+    // MPENV_POLICY_F32 (bit-equal to the reference, the default) or MPENV_POLICY_BF16 (the trunk and the
+    // heads on the bf16 matrix cores: for frozen opponents); any time, loaded or not, nothing is reloaded
+    void setPolicyPrecision(int precision) { check(mpenv_policy_set_precision(mgr_, precision)); }
+    int policyPrecision() const
+    {
+        int32_t p = 0;
+        check(mpenv_policy_precision(mgr_, &p));
+        return p;
+    }
     // every agent through policyId's checkpoint
     void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
     {

@@ -217,7 +217,7 @@ void mpenv_manager::runStep(hipStream_t st)
 {
     // evalAgentPolicy runs ahead of the game systems (sim.cpp:5361-5365);
     // in front of the captured graph, which a load or unload leaves alone
-    if (polLoaded) launched(launchPolicyStep(S, polDev, st), "policy launch failed");
+    if (polLoaded) launched(launchPolicyStep(S, polDev, st, kPolicyAll, polPrecision), "policy launch failed");
     preStep(st);
     launchStep(st);
     postStep(st);
@@ -1290,7 +1290,7 @@ int mpenv_policy_forward_slot(mpenv_manager *m, int32_t slot, float *logits, int
         return fail(MPENV_ERR_INVALID, slot == 0 ? std::string("no policy loaded (mpenv_policy_load)")
                                                  : "policy slot " + std::to_string(slot) +
                                                        " is empty (mpenv_policy_load_slot)");
-    if (launchPolicyForward(m->S, m->polDev, slot, logits, actions, streamOf(m, stream)))
+    if (launchPolicyForward(m->S, m->polDev, slot, logits, actions, streamOf(m, stream), m->polPrecision))
         return fail(MPENV_ERR_HIP, "policy launch failed");
     return MPENV_OK;
 }
@@ -1305,7 +1305,7 @@ int mpenv_debug_policy_step(mpenv_manager *m, int32_t parts, void *stream)
     if (!m) return fail(MPENV_ERR_INVALID, "null manager");
     if (!m->polLoaded) return fail(MPENV_ERR_INVALID, "no policy loaded (mpenv_policy_load)");
     if (parts < 1 || parts > kPolicyAll) return fail(MPENV_ERR_INVALID, "policy step: parts must be in [1, 7]");
-    if (launchPolicyStep(m->S, m->polDev, streamOf(m, stream), parts))
+    if (launchPolicyStep(m->S, m->polDev, streamOf(m, stream), parts, m->polPrecision))
         return fail(MPENV_ERR_HIP, "policy launch failed");
     return MPENV_OK;
 }
@@ -1325,6 +1325,53 @@ int mpenv_debug_policy_dense(mpenv_manager *m, const float *x, int32_t M, int32_
         DevPtr wp = DevPtr::create(packed.size() * sizeof(float));
         HIP_CHECK(hipMemcpyAsync(wp, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
         launched(launchPolicyDense(x, M, K, static_cast<const float *>(wp.get()), N, y, st),
+                 "policy dense launch failed");
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int mpenv_policy_set_precision(mpenv_manager *m, int32_t precision)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null manager");
+    if (precision != MPENV_POLICY_F32 && precision != MPENV_POLICY_BF16)
+        return fail(MPENV_ERR_INVALID, "policy precision " + std::to_string(precision) +
+                                           " is neither MPENV_POLICY_F32 (0) nor MPENV_POLICY_BF16 (1)");
+    m->polPrecision = precision;
+    return MPENV_OK;
+}
+
+int mpenv_policy_precision(mpenv_manager *m, int32_t *out)
+{
+    if (!m || !out) return fail(MPENV_ERR_INVALID, "null argument");
+    *out = m->polPrecision;
+    return MPENV_OK;
+}
+
+int mpenv_debug_policy_pack_bf16(const float *w, int32_t K, int32_t N, uint16_t *out, int64_t *count)
+{
+    if (!w || !count) return fail(MPENV_ERR_INVALID, "null argument");
+    if (K < 1 || N < 1) return fail(MPENV_ERR_INVALID, "policy pack: K, N >= 1");
+    *count = pol::packedBf16(K, N);
+    if (out) pol::packBf16(w, K, N, out);
+    return MPENV_OK;
+}
+
+int mpenv_debug_policy_dense_bf16(mpenv_manager *m, const float *x, int32_t M, int32_t K, const float *w_host,
+                                  int32_t N, float *y, void *stream)
+{
+    if (!m || !x || !w_host || !y) return fail(MPENV_ERR_INVALID, "null argument");
+    if (M < 1 || N < 1 || K < 1 || K > pol::kHidden)
+        return fail(MPENV_ERR_INVALID, "policy dense: M, N >= 1 and 1 <= K <= 512");
+    const int Np = (N + 63) / 64 * 64; // a wave takes two column tiles
+    std::vector<float> wide((size_t)K * Np, 0.f);
+    std::vector<uint16_t> packed((size_t)pol::packedBf16(K, Np));
+    for (int k = 0; k < K; k++) std::memcpy(&wide[(size_t)k * Np], &w_host[(size_t)k * N], sizeof(float) * (size_t)N);
+    pol::packBf16(wide.data(), K, Np, packed.data());
+    return guarded([&] {
+        hipStream_t st = streamOf(m, stream);
+        DevPtr wp = DevPtr::create(packed.size() * sizeof(uint16_t));
+        HIP_CHECK(hipMemcpyAsync(wp, packed.data(), packed.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        launched(launchPolicyDenseBf16(x, M, K, static_cast<const uint16_t *>(wp.get()), N, y, st),
                  "policy dense launch failed");
         HIP_CHECK(hipStreamSynchronize(st));
     });

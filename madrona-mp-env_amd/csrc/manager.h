@@ -247,6 +247,7 @@ struct mpenv_manager {
     const float *polBlobs[pol::kSlots] = {};
     int32_t *polTab = nullptr; // the allocation behind polDev's counters and tile tables
     bool polLoaded = false;
+    int32_t polPrecision = MPENV_POLICY_F32; // which trunk kernel runs (definition 15 or 16); every blob serves both
     // the last step was a gpuStreamStep that wrote the observation rows into
     // its caller's buffers only (OutTab): the engine's own rows, which the
     // policy, the aim-bot (mpenv_combat_actions) and a snapshot

@@ -24,6 +24,18 @@ void pol::packB(const float *w, int K, int N, float *out)
             }
 }
 
+void pol::packBf16(const float *w, int K, int N, uint16_t *out)
+{
+    const int steps = (K + 15) / 16, tiles = (N + 31) / 32;
+    for (int t = 0; t < tiles; t++)
+        for (int s = 0; s < steps; s++)
+            for (int l = 0; l < 64; l++)
+                for (int j = 0; j < 8; j++) {
+                    const int k = 16 * s + 8 * (l >> 5) + j, n = 32 * t + (l & 31);
+                    out[(((int64_t)t * steps + s) * 64 + l) * 8 + j] = (k < K && n < N) ? bf16Bits(w[(int64_t)k * N + n]) : 0;
+                }
+}
+
 namespace {
 
 struct Reader {
@@ -84,8 +96,10 @@ int policyRead(const char *dir, std::vector<float> *blob, std::string &err)
     Reader r;
     r.dir = dir;
     const Layout L = layout();
+    const LayoutBf16 B = layoutBf16();
     std::vector<float> out, t;
-    if (blob) out.assign((size_t)L.total, 0.f);
+    if (blob) out.assign((size_t)B.total, 0.f);
+    auto half = [&](int64_t at) { return reinterpret_cast<uint16_t *>(out.data() + at); };
     auto put = [&](int64_t at) {
         if (blob) std::memcpy(out.data() + at, t.data(), t.size() * sizeof(float));
     };
@@ -127,7 +141,10 @@ int policyRead(const char *dir, std::vector<float> *blob, std::string &err)
         const std::string base = "params_backbone_actor_encoder_net_MaxPoolNet_0_MLP_0_";
         const int K = i == 0 ? kTrunkIn : kHidden;
         if (!r.read(base + "Dense_" + std::to_string(i) + "_kernel", K, kHidden, t)) return err = r.err, r.code;
-        if (blob) packB(t.data(), K, kHidden, out.data() + L.trunkW[i]);
+        if (blob) {
+            packB(t.data(), K, kHidden, out.data() + L.trunkW[i]);
+            packBf16(t.data(), K, kHidden, half(B.trunkW[i]));
+        }
         if (!r.read(base + "LayerNorm_" + std::to_string(i) + "_impl_scale", kHidden, 0, t)) return err = r.err, r.code;
         put(L.trunkScale[i]);
         if (!r.read(base + "LayerNorm_" + std::to_string(i) + "_impl_bias", kHidden, 0, t)) return err = r.err, r.code;
@@ -149,6 +166,7 @@ int policyRead(const char *dir, std::vector<float> *blob, std::string &err)
     }
     if (blob) {
         packB(heads.data(), kHidden, kLogits, out.data() + L.headW);
+        packBf16(heads.data(), kHidden, kLogits, half(B.headW));
         blob->swap(out);
     }
     return MPENV_OK;

@@ -81,6 +81,41 @@ inline Layout layout()
 
 void packB(const float *w /*[K][N]*/, int K, int N, float *out /*packedFloats(K, N)*/);
 
+// bf16 precision (DESIGN.md §2 definition 17).  B-operand packing of a [K][N]
+// kernel for v_mfma_f32_32x32x16_bf16: column tile t (32 columns), k step s
+// (16 rows), lane l with r = l & 31, h = l >> 5 holds W[16 s + 8 h + j][32 t + r],
+// j = 0..7, as one 16-byte fragment at ((t * ceil(K/16) + s) * 64 + l) * 8 + j.
+// K is padded to a multiple of 16 and N to a multiple of 32 with +0.
+constexpr int64_t packedBf16(int K, int N) { return (int64_t)((N + 31) / 32) * ((K + 15) / 16) * 64 * 8; }
+// f32 -> bf16, round to nearest even; a NaN stays a (quiet) NaN
+inline uint16_t bf16Bits(float f)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &f, sizeof(u));
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+void packBf16(const float *w /*[K][N]*/, int K, int N, uint16_t *out /*packedBf16(K, N)*/);
+
+// The bf16 pieces of the blob, in floats, behind Layout::total: every blob
+// carries both packings, and no offset of Layout moves.
+struct LayoutBf16 {
+    int64_t trunkW[3]; // packBf16
+    int64_t headW;     // packBf16 [512][37 -> 64]
+    int64_t total;     // the whole blob
+};
+
+inline LayoutBf16 layoutBf16()
+{
+    LayoutBf16 B {};
+    int64_t o = layout().total;
+    auto take = [&](int64_t halves) { int64_t r = o; o += (halves / 2 + 63) / 64 * 64; return r; };
+    for (int i = 0; i < 3; i++) B.trunkW[i] = take(packedBf16(i == 0 ? kTrunkIn : kHidden, kHidden));
+    B.headW = take(packedBf16(kHidden, kHeadPad));
+    B.total = o;
+    return B;
+}
+
 } // namespace pol
 
 // policy.cpp: reads and validates a converted-checkpoint directory
@@ -130,10 +165,15 @@ struct PolicyDev {
 // parts: which of its kernels run (all in a step; mpenv_debug_policy_step times them apart --
 // the trunk alone reuses the list and the embeddings of the last full call).
 enum PolicyParts { kPolicySelect = 1, kPolicyEmbed = 2, kPolicyTrunk = 4, kPolicyAll = 7 };
-int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts = kPolicyAll);
+// precision: MPENV_POLICY_F32 (k_pol_trunk) or MPENV_POLICY_BF16 (k_pol_trunk_bf16); the other kernels are shared
+int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts = kPolicyAll,
+                     int precision = MPENV_POLICY_F32);
 // Every agent through the checkpoint of `slot`, no engine state written: logits [A][37], actions [A][6] (or null).
-int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream);
+int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream,
+                        int precision = MPENV_POLICY_F32);
 // y[M][N] = x[M][K] . w through the trunk's MFMA dense; wPacked = pol::packB(w) in device memory.
 int launchPolicyDense(const float *x, int M, int K, const float *wPacked, int N, float *y, void *stream);
+// the same through the bf16 trunk's dense; wPacked = pol::packBf16(w), N padded to a multiple of 64 columns
+int launchPolicyDenseBf16(const float *x, int M, int K, const uint16_t *wPacked, int N, float *y, void *stream);
 
 } // namespace mpenv

@@ -601,13 +601,259 @@ __global__ void __launch_bounds__(64) k_pol_dense(const float *x, int M, int K, 
             }
 }
 
+// ---- bf16 precision: k_pol_trunk_bf16 ---------------------------------------
+//
+// DESIGN.md §2 definition 17: dense inputs and weights rounded to bf16, exact
+// products, f32 accumulation in the order v_mfma_f32_32x32x16_bf16 takes,
+// LayerNorm over the unrounded f32 outputs.  The selection, the embed kernel,
+// the tile records and the sampling are the f32 path's; the tile's
+// activations are bf16 in LDS and the outputs stay in the accumulators until
+// they are normalised, so a block asks for half the LDS and two share a CU.
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef const __attribute__((address_space(1))) bf16x8 *FragPtr; // the packed weights, a lane's 16 bytes at a time
+
+constexpr int kLdb = 520;       // LDS row stride in bf16: 65 x 16 B, so the 16 lanes that ds_read_b128 serves
+                                // together (rows r, r + 1, ..) start at 16 different 16-B slots of the 256-B bank row
+constexpr int kLgStride = 65;   // the f32 logits over the activations, one row per lane
+constexpr size_t kActBytes = (size_t)kTileRows * kLdb * sizeof(uint16_t);
+constexpr size_t kTrunkLdsBf16 = kActBytes + (size_t)(8 * kTileRows + 2 * kTileRows) * sizeof(float);
+static_assert(kTrunkLdsBf16 <= 80 * 1024, "two blocks of k_pol_trunk_bf16 per CU (160 KiB of LDS)");
+static_assert((size_t)kTileRows * kLgStride * sizeof(float) <= kActBytes, "the logits fit over the activations");
+
+__device__ __forceinline__ uint16_t toBf16(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); } // RNE
+
+// acc[mt][nt] = X[row0 + 32 mt ..][0 .. 16 ksteps) . W[.., tile nt], X bf16 in
+// LDS (row stride kLdb), W packed (policy.h packBf16) with wp at the first
+// tile.  Lane l feeds A[l & 31][8 (l >> 5) + j] and B[8 (l >> 5) + j][l & 31].
+template <int MT, int NT>
+__device__ __forceinline__ void mfmaDenseBf16(const uint16_t *xs, int row0, int ksteps, FragPtr wp, f32x16 (&acc)[MT][NT])
+{
+    const int lane = threadIdx.x & 63;
+    const uint16_t *xa = xs + (row0 + (lane & 31)) * kLdb + 8 * (lane >> 5);
+    const FragPtr wb = wp + lane;
+    const int64_t tileStride = (int64_t)ksteps * 64;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) acc[mt][nt][v] = 0.f;
+    bf16x8 b[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; nt++) b[nt] = wb[nt * tileStride];
+    for (int s = 0; s < ksteps; s++) {
+        // the next step's weights are in flight while this step's MFMAs run (the last step loads itself again)
+        const int sn = s + 1 < ksteps ? s + 1 : s;
+        bf16x8 bn[NT], a[MT];
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) bn[nt] = wb[nt * tileStride + (int64_t)sn * 64];
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++) a[mt] = *reinterpret_cast<const bf16x8 *>(xa + mt * 32 * kLdb + 16 * s);
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++)
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) b[nt] = bn[nt];
+    }
+}
+
+// the row of accumulator register v of tile mt in a lane of half h (the C/D map above storeTiles)
+__device__ __forceinline__ int accRow(int mt, int v, int h) { return 32 * mt + 8 * (v >> 2) + 4 * h + (v & 3); }
+
+// v + the v of the lane that the DPP control names (0xb1: lane ^ 1, 0x4e: lane ^ 2 in a quad;
+// 0x141, 0x140: the mirror image in the lane's 8 and 16)
+template <int kCtrl>
+__device__ __forceinline__ float addDpp(float v)
+{
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), kCtrl, 0xf, 0xf, false));
+}
+
+// the sum of v over the 32 lanes of the lane's half, in every one of them
+__device__ __forceinline__ float halfSum(float v)
+{
+    v = addDpp<0xb1>(v);
+    v = addDpp<0x4e>(v);
+    v = addDpp<0x141>(v);
+    v = addDpp<0x140>(v);
+    return v + __shfl_xor(v, 16);
+}
+
+// The sum over a row's 512 outputs of f(acc), for all 64 rows: the lane's two
+// column tiles, the 32 lanes of a half, then the eight waves through `part`
+// (lane l of a wave writes the row of register l & 15 of row tile (l >> 4) & 1).
+// fin(sum) of row tid goes to out[tid]; the block has passed a barrier when
+// this returns.
+template <typename F, typename G>
+__device__ __forceinline__ void rowStat(const f32x16 (&acc)[2][2], float *part, float *out, F f, G fin)
+{
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float mine = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const float sum = halfSum(f(acc[mt][0][r]) + f(acc[mt][1][r]));
+            if ((lane & 31) == 16 * mt + r) mine = sum;
+        }
+    part[wave * kTileRows + accRow((lane >> 4) & 1, lane & 15, lane >> 5)] = mine;
+    __syncthreads();
+    if (tid < kTileRows) {
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; w++) t += part[w * kTileRows + tid];
+        out[tid] = fin(t);
+    }
+    __syncthreads();
+}
+
+// Same grid, tile records, fwdSlot convention and outputs as k_pol_trunk.
+__global__ void __launch_bounds__(kTrunkThreads, 4) k_pol_trunk_bf16(DevState S, PolicyDev P, Layout L, LayoutBf16 B,
+                                                                     int fwdSlot, float *logitsOut, int32_t *actionsOut)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    uint16_t *xs = reinterpret_cast<uint16_t *>(lds);    // [64][kLdb] activations, bf16
+    float *part = lds + kActBytes / sizeof(float);       // [8 waves][64 rows] partial row sums
+    float *mean = part + 8 * kTileRows, *sigma = mean + kTileRows;
+    float *lgs = lds;                                    // [64][kLgStride] logits, once the heads have read xs
+
+    const bool useList = fwdSlot < 0;
+    const int64_t base = (int64_t)blockIdx.x * kTileRows;
+    int64_t n = S.A; // one past the tile's last live row
+    BlobPtr blob;
+    if (useList) {
+        const Tile t = P.tiles[blockIdx.x];
+        blob = (BlobPtr)t.blob;
+        n = base + t.rows;
+    } else {
+        blob = (BlobPtr)P.blobs[fwdSlot];
+    }
+    if (base >= n) return; // past the list
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5;
+
+    for (int idx = tid; idx < kTileRows * (kTrunkIn / 2); idx += kTrunkThreads) { // the f32 trunk inputs, two at a time
+        const int r = idx / (kTrunkIn / 2), c = 2 * (idx - r * (kTrunkIn / 2));
+        float2 x = make_float2(0.f, 0.f);
+        if (base + r < n) x = *reinterpret_cast<const float2 *>(P.emb + (base + r) * kTrunkIn + c);
+        *reinterpret_cast<uint32_t *>(xs + r * kLdb + c) = (uint32_t)toBf16(x.x) | ((uint32_t)toBf16(x.y) << 16);
+    }
+    __syncthreads();
+
+    for (int layer = 0; layer < 3; layer++) {
+        const int ksteps = (layer == 0 ? kTrunkIn : kHidden) / 16;
+        f32x16 acc[2][2];
+        mfmaDenseBf16<2, 2>(xs, 0, ksteps, (FragPtr)(blob + B.trunkW[layer]) + (int64_t)(2 * wave) * ksteps * 64, acc);
+        // mean, then the biased variance of the deviations, over the unrounded outputs
+        rowStat(acc, part, mean, [](float y) { return y; }, [](float t) { return t * (1.f / (float)kHidden); });
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const float m = mean[accRow(mt, v, half)];
+                acc[mt][0][v] -= m;
+                acc[mt][1][v] -= m;
+            }
+        rowStat(acc, part, sigma, [](float d) { return d * d; },
+                [](float t) { return mp::sqrt_(t / (float)kHidden + 1e-6f); });
+        // every wave is past its MFMAs: the tile's inputs make way for its outputs
+        const int col = 64 * wave + (lane & 31);
+        const float sc[2] = { blob[L.trunkScale[layer] + col], blob[L.trunkScale[layer] + col + 32] };
+        const float bs[2] = { blob[L.trunkBias[layer] + col], blob[L.trunkBias[layer] + col + 32] };
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const int r = accRow(mt, v, half);
+                const float sg = sigma[r];
+#pragma unroll
+                for (int nt = 0; nt < 2; nt++) {
+                    const float o = mp::fma_(sc[nt] / sg, acc[mt][nt][v], bs[nt]);
+                    xs[r * kLdb + col + 32 * nt] = toBf16(o >= 0.f ? o : 0.f * o);
+                }
+            }
+        __syncthreads();
+    }
+
+    // both heads as one 512 x 64 dense: four waves, one 32 x 32 tile each
+    f32x16 hacc[1][1];
+    const int mt = wave & 1, nt = (wave >> 1) & 1;
+    if (wave < 4) mfmaDenseBf16<1, 1>(xs, 32 * mt, kHidden / 16, (FragPtr)(blob + B.headW) + (int64_t)nt * (kHidden / 16) * 64, hacc);
+    __syncthreads();
+    if (wave < 4)
+#pragma unroll
+        for (int v = 0; v < 16; v++) lgs[accRow(mt, v, half) * kLgStride + 32 * nt + (lane & 31)] = hacc[0][0][v];
+    __syncthreads();
+
+    // from here on as k_pol_trunk: bias, logits out, the six draws
+    if (tid >= kTileRows || base + tid >= n) return;
+    const int64_t g = useList ? (int64_t)P.list[base + tid] : base + tid;
+    float *lg = lgs + tid * kLgStride; // the agent's own row
+    for (int j = 0; j < kLogits; j++) lg[j] = lg[j] + blob[L.headBias + j];
+    if (logitsOut)
+        for (int j = 0; j < kLogits; j++) logitsOut[g * kLogits + j] = lg[j];
+    if (!useList && !actionsOut) return;
+
+    constexpr int kBuckets[kNumHeads] = { 3, 8, 3, 3, 13, 7 };
+    mp::RNG rng;
+    rng.key.a = (uint32_t)S.rngA[g];
+    rng.key.b = (uint32_t)S.rngB[g];
+    rng.ctr = (uint32_t)S.rngCtr[g];
+    int32_t act[kNumHeads];
+    int at = 0;
+#pragma unroll
+    for (int h = 0; h < kNumHeads; h++) {
+        act[h] = sampleHead(lg + at, kBuckets[h], mp::rngAdvance(rng));
+        at += kBuckets[h];
+    }
+    if (useList) {
+        reinterpret_cast<int4 *>(S.discreteAction)[g] = make_int4(act[0], act[1], act[2], act[3]);
+        reinterpret_cast<int2 *>(S.discreteAim)[g] = make_int2(act[4], act[5]);
+        S.rngCtr[g] = (int32_t)rng.ctr;
+    } else {
+        for (int h = 0; h < kNumHeads; h++) actionsOut[g * kNumHeads + h] = act[h];
+    }
+}
+
+// mpenv_debug_policy_dense_bf16: one wave per 64 x 64 output tile through mfmaDenseBf16
+__global__ void __launch_bounds__(64) k_pol_dense_bf16(const float *x, int M, int K, const uint16_t *wp, int N, float *y)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    uint16_t *xs = reinterpret_cast<uint16_t *>(lds);
+    const int lane = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
+    const int Kp = (K + 15) & ~15;
+    for (int idx = lane; idx < kTileRows * Kp; idx += 64) {
+        const int r = idx / Kp, c = idx - r * Kp;
+        xs[r * kLdb + c] = toBf16((row0 + r < M && c < K) ? x[(row0 + r) * K + c] : 0.f);
+    }
+    __syncthreads();
+    f32x16 acc[2][2];
+    mfmaDenseBf16<2, 2>(xs, 0, Kp / 16, (FragPtr)wp + (int64_t)(2 * blockIdx.y) * (Kp / 16) * 64, acc);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int nt = 0; nt < 2; nt++)
+#pragma unroll
+            for (int v = 0; v < 16; v++) {
+                const int64_t r = row0 + accRow(mt, v, lane >> 5);
+                const int c = 64 * blockIdx.y + 32 * nt + (lane & 31);
+                if (r < M && c < N) y[r * N + c] = acc[mt][nt][v];
+            }
+}
+
 int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
 
 int run(const DevState &s, const PolicyDev &p, int fwdSlot, float *logits, int32_t *actions, hipStream_t st,
-        int parts = kPolicyEmbed | kPolicyTrunk)
+        int precision, int parts = kPolicyEmbed | kPolicyTrunk)
 {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_pol_trunk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kTrunkLds) != hipSuccess)
+    const bool bf16 = precision == MPENV_POLICY_BF16;
+    if (!bf16 && precision != MPENV_POLICY_F32) return -1;
+    if (hipFuncSetAttribute(bf16 ? reinterpret_cast<const void *>(k_pol_trunk_bf16)
+                                 : reinterpret_cast<const void *>(k_pol_trunk),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(bf16 ? kTrunkLdsBf16 : kTrunkLds)) != hipSuccess)
         return -1;
     const Layout L = layout();
     const int64_t perBlock = kEmbedWaves * kEmbedAgents;
@@ -617,14 +863,18 @@ int run(const DevState &s, const PolicyDev &p, int fwdSlot, float *logits, int32
                            st, s, p, L, fwdSlot);
     if (check(hipGetLastError())) return -1;
     if (!(parts & kPolicyTrunk)) return 0;
-    hipLaunchKernelGGL(k_pol_trunk, dim3((unsigned)((rows + kTileRows - 1) / kTileRows)), dim3(kTrunkThreads), kTrunkLds,
-                       st, s, p, L, fwdSlot, logits, actions);
+    const dim3 tiles((unsigned)((rows + kTileRows - 1) / kTileRows));
+    if (bf16)
+        hipLaunchKernelGGL(k_pol_trunk_bf16, tiles, dim3(kTrunkThreads), kTrunkLdsBf16, st, s, p, L, layoutBf16(),
+                           fwdSlot, logits, actions);
+    else
+        hipLaunchKernelGGL(k_pol_trunk, tiles, dim3(kTrunkThreads), kTrunkLds, st, s, p, L, fwdSlot, logits, actions);
     return check(hipGetLastError());
 }
 
 } // namespace
 
-int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts)
+int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int parts, int precision)
 {
     hipStream_t st = (hipStream_t)stream;
     if (parts & kPolicySelect) {
@@ -635,13 +885,14 @@ int launchPolicyStep(const DevState &s, const PolicyDev &p, void *stream, int pa
         hipLaunchKernelGGL(k_pol_scatter, grid, dim3(kSelThreads), 0, st, s, p);
         if (check(hipGetLastError())) return -1;
     }
-    return run(s, p, -1, nullptr, nullptr, st, parts);
+    return run(s, p, -1, nullptr, nullptr, st, precision, parts);
 }
 
-int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream)
+int launchPolicyForward(const DevState &s, const PolicyDev &p, int slot, float *logits, int32_t *actions, void *stream,
+                        int precision)
 {
     if (slot < 0 || slot >= kSlots || !((p.mask >> slot) & 1u)) return -1;
-    return run(s, p, slot, logits, actions, (hipStream_t)stream);
+    return run(s, p, slot, logits, actions, (hipStream_t)stream, precision);
 }
 
 // wPacked: pol::packB of w with N padded to a multiple of 64 columns
@@ -653,6 +904,18 @@ int launchPolicyDense(const float *x, int M, int K, const float *wPacked, int N,
         return -1;
     hipLaunchKernelGGL(k_pol_dense, dim3((unsigned)((M + kTileRows - 1) / kTileRows), (unsigned)((N + 63) / 64)),
                        dim3(64), kDenseLds, (hipStream_t)stream, x, M, K, wPacked, N, y);
+    return check(hipGetLastError());
+}
+
+// wPacked: pol::packBf16 of w with N padded to a multiple of 64 columns
+int launchPolicyDenseBf16(const float *x, int M, int K, const uint16_t *wPacked, int N, float *y, void *stream)
+{
+    if (M < 1 || N < 1 || K < 1 || K > kHidden) return -1;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_pol_dense_bf16), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kActBytes) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(k_pol_dense_bf16, dim3((unsigned)((M + kTileRows - 1) / kTileRows), (unsigned)((N + 63) / 64)),
+                       dim3(64), kActBytes, (hipStream_t)stream, x, M, K, wPacked, N, y);
     return check(hipGetLastError());
 }
 

@@ -187,13 +187,21 @@ PYBIND11_MODULE(madrona_mp_env, m)
             return from_dlpack(t.dlpack());
         });
 
+    // "f32" / "bf16" <-> MPENV_POLICY_F32 / MPENV_POLICY_BF16
+    auto precision_of = [](const std::string &name) -> int32_t {
+        if (name == "f32") return MPENV_POLICY_F32;
+        if (name == "bf16") return MPENV_POLICY_BF16;
+        throw std::invalid_argument("policy precision must be \"f32\" or \"bf16\", not \"" + name + "\"");
+    };
+
     py::class_<PySimManager>(m, "SimManager")
-        .def(py::init([](ExecMode exec_mode, int64_t gpu_id, int64_t num_worlds, int64_t rand_seed, bool auto_reset,
+        .def(py::init([precision_of](ExecMode exec_mode, int64_t gpu_id, int64_t num_worlds, int64_t rand_seed, bool auto_reset,
                          uint32_t sim_flags, Task task, uint32_t team_size, uint32_t num_pbt_policies,
                          uint32_t policy_history_size, const std::string &scene_path, bool train_flank,
                          py::object replay_log_path, py::object record_log_path, py::object event_log_path,
                          py::object curriculum_data_path, uint32_t world_id_offset,
-                         py::object policy_weights_path) {
+                         py::object policy_weights_path, const std::string &policy_precision) {
+                 const int32_t precision = precision_of(policy_precision);
                  std::string replay, record, event, curric, weights;
                  mpenv_config cfg = {};
                  cfg.exec_mode = (int32_t)exec_mode;
@@ -221,6 +229,7 @@ PYBIND11_MODULE(madrona_mp_env, m)
                      py::gil_scoped_release nogil;
                      check(mpenv_create(&cfg, &h->mgr));
                  }
+                 check(mpenv_policy_set_precision(h->mgr, precision));
                  // Manager::Config::policyWeightsPath (mgr.hpp:49): loaded after the create, failing loudly;
                  // a {policy_id: dir} dict loads one checkpoint per id (mpenv_policy_slots.h)
                  if (py::isinstance<py::dict>(policy_weights_path)) {
@@ -240,7 +249,7 @@ PYBIND11_MODULE(madrona_mp_env, m)
              py::arg("train_flank") = false, py::arg("replay_log_path") = py::none(),
              py::arg("record_log_path") = py::none(), py::arg("event_log_path") = py::none(),
              py::arg("curriculum_data_path") = py::none(), py::arg("world_id_offset") = 0,
-             py::arg("policy_weights_path") = py::none())
+             py::arg("policy_weights_path") = py::none(), py::arg("policy_precision") = "f32")
         .def("init", [](PySimManager &s) { py::gil_scoped_release nogil; check(mpenv_init(s.h->mgr)); })
         .def("step", [](PySimManager &s) { py::gil_scoped_release nogil; check(mpenv_step(s.h->mgr)); })
         .def("step_async", [](PySimManager &s, uintptr_t stream) {
@@ -297,6 +306,15 @@ PYBIND11_MODULE(madrona_mp_env, m)
             check(policy_id.is_none() ? mpenv_policy_unload(s.h->mgr)
                                       : mpenv_policy_unload_slot(s.h->mgr, policy_id.cast<int32_t>()));
         }, py::arg("policy_id") = py::none())
+        // "f32" (bit-equal to the reference) or "bf16" (trunk and heads on the bf16 matrix cores)
+        .def("set_policy_precision", [precision_of](PySimManager &s, const std::string &name) {
+            check(mpenv_policy_set_precision(s.h->mgr, precision_of(name)));
+        }, py::arg("precision"))
+        .def("policy_precision", [](PySimManager &s) {
+            int32_t p = 0;
+            check(mpenv_policy_precision(s.h->mgr, &p));
+            return std::string(p == MPENV_POLICY_BF16 ? "bf16" : "f32");
+        })
         .def("policy_slots", [](PySimManager &s) {
             uint32_t mask = 0;
             check(mpenv_policy_slots(s.h->mgr, &mask));
