@@ -690,6 +690,9 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
 /* the precision switch: MPENV_POLICY_F32, MPENV_POLICY_BF16, mpenv_policy_set_precision,
  * mpenv_policy_precision and the bf16 test hooks */
 #include "mpenv_policy_precision.h"
+/* scene residency: MPENV_SCENE_AUTO / _LDS / _GLOBAL, mpenv_set_scene_residency,
+ * mpenv_scene_residency, and mpenv_scene_info with mpenv_scene_info_t */
+#include "mpenv_scene_residency.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

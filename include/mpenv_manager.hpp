@@ -221,6 +221,16 @@ public:
         check(mpenv_policy_precision(mgr_, &p));
         return p;
     }
+    // extension: scene residency (mpenv_scene_residency.h).  MPENV_SCENE_AUTO, MPENV_SCENE_LDS (throws on a
+    // scene that does not fit) or MPENV_SCENE_GLOBAL; between steps, the step graph is re-captured by the next
+    void setSceneResidency(int mode) { check(mpenv_set_scene_residency(mgr_, mode)); }
+    // the path in use: MPENV_SCENE_LDS or MPENV_SCENE_GLOBAL
+    int sceneResidency() const
+    {
+        int32_t mode = 0;
+        check(mpenv_scene_residency(mgr_, &mode));
+        return mode;
+    }
     // every agent through policyId's checkpoint
     void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
     {

@@ -29,7 +29,8 @@ ORACLE_LIB = os.path.join(ORACLE, "_build", "liboracle.so")
 LIB_SOURCES = ["kernels.hip", "wire.hip", "state.hip", "policy.hip", "manager.cpp", "manager_scene.cpp", "policy.cpp",
                "scene.cpp", "navmesh.cpp"]
 LIB_HEADERS = ["mpenv_core.h", "engine.h", "geom_dev.h", "scene.h", "policy.h", "manager.h"]
-API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h", "mpenv_policy_precision.h")]
+API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h", "mpenv_policy_precision.h",
+                                                     "mpenv_scene_residency.h")]
 
 
 def _stale(out, deps):

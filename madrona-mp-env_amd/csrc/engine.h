@@ -41,7 +41,12 @@ constexpr int kRearRays = 16;  // 2 x 8
 constexpr int kLidarRays = kFwdRays + kRearRays;
 constexpr int kMaxCrumbs = 128;
 constexpr int kMinSpawnTrack = 128; // SpawnUsageCounter::maxNumSpawns (types.hpp:96)
-constexpr int kMaxBVHStack = 16; // register byte-stack capacity
+constexpr int kMaxBVHStack = 16; // register byte-stack capacity (LDS-resident scenes)
+constexpr int kMaxGlobalStack = 64; // WideStack capacity (global-resident scenes); the oracle's stack holds as many
+constexpr int kMaxLdsNodes = 256;   // a byte-stack entry holds a node index
+// k_vis's occluder hints are uint16_t triangle indices, 0xffff = none
+constexpr int kMaxSceneTris = 0xfffe;
+constexpr size_t kLdsBudget = 64 * 1024; // dynamic LDS a block may ask for without a function attribute
 
 #define MP_AGENT_F32(X) \
     X(px) X(py) X(pz) X(vx) X(vy) X(vz) X(rw) X(rx) X(ry) X(rz) \
@@ -351,6 +356,18 @@ struct SceneDev {
     int32_t qgW, qgH;
 };
 
+// Scene residency: the images stageBVHSphere and
+// stageBVHOct build, built once in global memory by k_scene_images, and
+// which of the two the kernels walk.  Beside SceneDev, not in it: the
+// LDS-resident kernels' arguments are what they were, and only the global
+// instantiations take this as one more.
+enum : int32_t { kResidencyLds = 0, kResidencyGlobal = 1 };
+struct SceneImages {
+    char *sphere; // bvhLdsBytesSphere bytes; begins with stageBVH's image
+    char *oct;    // bvhLdsBytesOct bytes
+    int32_t residency;
+};
+
 // Host launchers (kernels.hip)
 struct LaunchCtx {
     void *stream;       // hipStream_t
@@ -364,12 +381,21 @@ const char *kernelName(int k);
 size_t bvhLdsBytes(const SceneDev &sc);
 size_t bvhLdsBytesSphere(const SceneDev &sc); // + triPre (sphere-casting kernels)
 size_t bvhLdsBytesOct(const SceneDev &sc);    // octant node images + vertices (k_lidar)
+// The dynamic LDS each step kernel asks for under a residency (only the
+// scene's counts are read, so a SceneDev without device pointers will do).
+// k_vis's also depends on the team size; T = 0: the largest over all of them.
+size_t moveLdsBytes(const SceneDev &sc, int32_t residency);
+size_t simLdsBytes(const SceneDev &sc, int32_t residency);
+size_t visLdsBytes(const SceneDev &sc, int32_t residency, int T);
+size_t lidarLdsBytes(const SceneDev &sc, int32_t residency);
+// Fills img.sphere / img.oct; synchronous on `stream`
+int buildSceneImages(const SceneDev &sc, const SceneImages &img, void *stream);
 
 int launchConstruct(const DevState &s, const SceneDev &sc, const int32_t ctor_train_ctrl[3], void *stream);
 int launchResetOnly(const DevState &s, const SceneDev &sc, void *stream);
-int launchMove(const DevState &s, const SceneDev &sc, void *stream);
-int launchSimStep(const DevState &s, const SceneDev &sc, void *stream);
-int launchVisibility(const DevState &s, const SceneDev &sc, void *stream);
+int launchMove(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream);
+int launchSimStep(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream);
+int launchVisibility(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream);
 int launchObservations(const DevState &s, const SceneDev &sc, void *stream);
 // k_obs over a wire message (wire.hip launchWireUnpack): `view` is the
 // shadow's DevState with its input columns pointing into the message.
@@ -383,13 +409,14 @@ int launchObservationsWire(const DevState &view, const SceneDev &sc, const WireO
 // lidarItersMax(); lidarItersFor is the automatic choice for A agents.
 int lidarItersMax();
 int lidarItersFor(int64_t A);
-int launchLidar(const DevState &s, const SceneDev &sc, int iters, void *stream);
+int launchLidar(const DevState &s, const SceneDev &sc, const SceneImages &img, int iters, void *stream);
 // synchronous on `stream`, at scene upload; dev_scratch holds kMaxZones ints
 int computeZoneGoalTris(const SceneDev &sc, int32_t *dev_scratch, int32_t *host_out, void *stream);
-int launchTraceRays(const SceneDev &sc, const float *o, const float *d, int n, int mode, float *t, int32_t *hit,
-                    void *stream);
+int launchTraceRays(const SceneDev &sc, const SceneImages &img, const float *o, const float *d, int n, int mode,
+                    float *t, int32_t *hit, void *stream);
 // mpenv_debug_geom_queries (include/mpenv.h)
-int launchGeomQueries(const SceneDev &sc, int mode, int n, const mpenv_geom_queries &q, void *stream);
+int launchGeomQueries(const SceneDev &sc, const SceneImages &img, int mode, int n, const mpenv_geom_queries &q,
+                      void *stream);
 int launchDebugGather(const DevState &s, float *af, int32_t *ai, int32_t *wi, float *wf, uint32_t *explore,
                       float *crumbs, void *stream);
 int launchFillActions(const DevState &s, const int32_t *src6, void *stream);

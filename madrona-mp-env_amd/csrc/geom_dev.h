@@ -9,7 +9,10 @@
 //   * the traversal stack is a 16-entry byte stack held in two 64-bit
 //     registers (node indices < 256) — no scratch memory, no LDS stack;
 //   * child-visit order and every float expression match the reference
-//     (and the CPU oracle) exactly, so hits are bit-identical.
+//     (and the CPU oracle) exactly, so hits are bit-identical;
+//   * a scene too large for that is walked from the same images built once
+//     in global memory, with a 64-entry stack in private memory: the second
+//     instantiation (LBVHG) of everything below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,13 +23,27 @@
 
 namespace mpenv {
 
-#define MP_LDS __attribute__((address_space(3)))
+// Where a kernel's BVH images live ("Scene residency").
+// Every function below that reads an image is a template over LBVH, the view
+// type, and is instantiated twice from this one source:
+//   LBVHL  the images staged into the block's dynamic LDS (address space 3,
+//          ds_read), node indices < 256 on the 16-entry register ByteStack;
+//   LBVHG  the images built once at scene upload in global memory (address
+//          space 1, global_load, L2-resident), node indices on the
+//          kMaxGlobalStack-entry WideStack.
+// MP_LDS is the address space of the LBVH in scope, so the same expressions
+// in the same order run on either.
+#define MP_LDS __attribute__((address_space(LBVH::kAS)))
 
-struct LBVH {
-    const MP_LDS BVHNode *nodes;
-    const MP_LDS float *verts;
-    const MP_LDS float *pre; // sphere-casting kernels only (stageBVHSphere)
-    const MP_LDS float *snodes; // sphere-cast node image (stageBVHSphere), else null
+template <int kAS_, bool kStaged_, class Stack_>
+struct LBVHT {
+    static constexpr int kAS = kAS_;
+    static constexpr bool kStaged = kStaged_; // the kernel copies the image into its LDS first
+    using Stack = Stack_;
+    const __attribute__((address_space(kAS_))) BVHNode *nodes;
+    const __attribute__((address_space(kAS_))) float *verts;
+    const __attribute__((address_space(kAS_))) float *pre; // sphere-casting kernels only (stageBVHSphere)
+    const __attribute__((address_space(kAS_))) float *snodes; // sphere-cast node image (stageBVHSphere), else null
     unsigned long long *stats;  // workload counters (DevState::stats), null = off
     int32_t rotStride;          // stageBVHOct: float4s per rotated vertex copy
 };
@@ -62,6 +79,11 @@ struct ByteStack {
     int n;
 };
 
+__device__ __forceinline__ void bsInit(ByteStack &s)
+{
+    s.lo = 0; s.hi = 0; s.n = 0;
+}
+
 __device__ __forceinline__ void bsPush(ByteStack &s, uint32_t v)
 {
     s.hi = (s.hi << 8) | (s.lo >> 56);
@@ -78,12 +100,63 @@ __device__ __forceinline__ uint32_t bsPop(ByteStack &s)
     return v;
 }
 
+// bvhSphereCast2D's entries carry 2 bits beside the node: which of its two
+// casts entered it.  The byte stack keeps them in a word of its own (16
+// entries x 2 bits).
+__device__ __forceinline__ void bsPush2(ByteStack &s, uint32_t &ms, uint32_t v, uint32_t pass)
+{
+    bsPush(s, v);
+    ms = (ms << 2) | pass;
+}
+
+__device__ __forceinline__ uint32_t bsPop2(ByteStack &s, uint32_t &ms, uint32_t &m)
+{
+    const uint32_t v = bsPop(s);
+    m = ms & 3u;
+    ms >>= 2;
+    return v;
+}
+
+// The global-resident path's stack: kMaxGlobalStack 32-bit entries per lane
+// in private memory (scratch), any node index, bvhSphereCast2D's 2 bits in
+// an entry's top bits.  Not in LDS: k_lidar's 1024-lane blocks would need
+// 128 KB for 64 16-bit entries per lane, above the 64 KB a block gets; not in
+// registers: 64 entries are 32 VGPRs, half of k_lidar's budget (DESIGN.md
+// section 3).  The host refuses a scene whose stack bound exceeds the
+// capacity (manager_scene.cpp sceneLimits), so no push is bounds-checked.
+struct WideStack {
+    uint32_t v[kMaxGlobalStack];
+    int n;
+};
+
+__device__ __forceinline__ void bsInit(WideStack &s) { s.n = 0; }
+
+__device__ __forceinline__ void bsPush(WideStack &s, uint32_t v) { s.v[s.n++] = v; }
+
+__device__ __forceinline__ uint32_t bsPop(WideStack &s) { return s.v[--s.n]; }
+
+__device__ __forceinline__ void bsPush2(WideStack &s, uint32_t &, uint32_t v, uint32_t pass) { bsPush(s, v | (pass << 30)); }
+
+__device__ __forceinline__ uint32_t bsPop2(WideStack &s, uint32_t &, uint32_t &m)
+{
+    const uint32_t v = bsPop(s);
+    m = v >> 30;
+    return v & 0x3fffffffu;
+}
+
+using LBVHL = LBVHT<3, true, ByteStack>;
+using LBVHG = LBVHT<1, false, WideStack>;
+
 // Stage nodes + vertices into dynamic LDS (all threads participate).
 // LDS image: nodes verbatim (64 B each), then every triangle vertex padded
 // to a float4 so a triangle is three ds_read_b128.
 // The collision tree: every query but the lidar's walks it (k_vis walked
 // the lidar tree in round 6 and is back: a sight answer can depend on the
 // tree, DESIGN.md section 2 definition 4).
+// kWrite: build the image at `smem`; without it (the global-resident path)
+// `smem` is the image k_scene_images built with these same loops at scene
+// upload (SceneImages), and only the view and the barrier are left.
+template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVH(char *smem, const SceneDev &sc)
 {
     const int numNodes = sc.numNodes;
@@ -91,11 +164,13 @@ __device__ __forceinline__ LBVH stageBVH(char *smem, const SceneDev &sc)
     const int node_q = numNodes * 4; // uint4 per node
     const uint4 *src_n = reinterpret_cast<const uint4 *>(sc.nodes);
     uint4 *dst_n = reinterpret_cast<uint4 *>(smem);
-    for (int k = threadIdx.x; k < node_q; k += blockDim.x) dst_n[k] = src_n[k];
+    if constexpr (kWrite)
+        for (int k = threadIdx.x; k < node_q; k += blockDim.x) dst_n[k] = src_n[k];
     const float *src_v = sc.verts;
     float4 *dst_v = reinterpret_cast<float4 *>(smem + (size_t)node_q * 16);
-    for (int k = threadIdx.x; k < numVerts; k += blockDim.x)
-        dst_v[k] = make_float4(src_v[3 * k], src_v[3 * k + 1], src_v[3 * k + 2], 0.f);
+    if constexpr (kWrite)
+        for (int k = threadIdx.x; k < numVerts; k += blockDim.x)
+            dst_v[k] = make_float4(src_v[3 * k], src_v[3 * k + 1], src_v[3 * k + 2], 0.f);
     __syncthreads();
     LBVH b;
     b.nodes = (const MP_LDS BVHNode *)(smem);
@@ -109,13 +184,15 @@ __device__ __forceinline__ LBVH stageBVH(char *smem, const SceneDev &sc)
 
 // stageBVH plus the per-triangle sphere-cast constants (SceneDev::triPre,
 // two float4 per triangle) after the vertices.
+template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
 {
     const size_t pre_off = (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16;
     const int pre_q = (sc.numVerts / 3) * 2;
     const float4 *src_p = reinterpret_cast<const float4 *>(sc.triPre);
     float4 *dst_p = reinterpret_cast<float4 *>(smem + pre_off);
-    for (int k = threadIdx.x; k < pre_q; k += blockDim.x) dst_p[k] = src_p[k];
+    if constexpr (kWrite)
+        for (int k = threadIdx.x; k < pre_q; k += blockDim.x) dst_p[k] = src_p[k];
     // Sphere-cast node image (kSNodeFloats per node): per axis a, the
     // children's dequantised slab ends already widened by the cast radius,
     // loR[a][i] = (min_a + 2^e_a * qMin_a[i]) - r and
@@ -125,7 +202,7 @@ __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
     // k_move cast uses the agent radius).
     const size_t sn_off = pre_off + (size_t)(sc.numVerts / 3) * 32;
     float *sn = reinterpret_cast<float *>(smem + sn_off);
-    for (int k = threadIdx.x; k < sc.numNodes * 4; k += blockDim.x) {
+    for (int k = threadIdx.x; kWrite && k < sc.numNodes * 4; k += blockDim.x) {
         const int n = k >> 2, i = k & 3;
         const BVHNode &nd = sc.nodes[n];
         float *o = sn + (size_t)n * kSNodeFloats;
@@ -153,7 +230,7 @@ __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
         }
         o[28 + i] = __uint_as_float((uint32_t)cnt);
     }
-    LBVH b = stageBVH(smem, sc); // ends with __syncthreads
+    LBVH b = stageBVH<LBVH, kWrite>(smem, sc); // ends with __syncthreads
     b.pre = (const MP_LDS float *)(smem + pre_off);
     b.snodes = (const MP_LDS float *)(smem + sn_off);
     return b;
@@ -170,16 +247,18 @@ __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
 // gathers: k_lidar 0.730 -> 0.744 ms, round 3).
 constexpr int kOctNodeQ = 4;
 
+template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVHOct(char *smem, const SceneDev &sc)
 {
     const int node_q = sc.numLidarNodes * kOctNodeQ * 8;
     const uint4 *src_n = reinterpret_cast<const uint4 *>(sc.octNodes);
     uint4 *dst_n = reinterpret_cast<uint4 *>(smem);
-    for (int k = threadIdx.x; k < sc.numLidarNodes * 4 * 8; k += blockDim.x)
-        dst_n[(k >> 2) * kOctNodeQ + (k & 3)] = src_n[k];
+    if constexpr (kWrite)
+        for (int k = threadIdx.x; k < sc.numLidarNodes * 4 * 8; k += blockDim.x)
+            dst_n[(k >> 2) * kOctNodeQ + (k & 3)] = src_n[k];
     const float *src_v = sc.lidarVerts;
     float4 *dst_v = reinterpret_cast<float4 *>(smem + (size_t)node_q * 16);
-    for (int k = threadIdx.x; k < sc.numLidarVerts * 3; k += blockDim.x) {
+    for (int k = threadIdx.x; kWrite && k < sc.numLidarVerts * 3; k += blockDim.x) {
         const int r = k / sc.numLidarVerts, v = k - r * sc.numLidarVerts;
         const int r1 = r == 2 ? 0 : r + 1, r2 = r1 == 2 ? 0 : r1 + 1;
         dst_v[k] = make_float4(src_v[3 * v + r1], src_v[3 * v + r2], src_v[3 * v + r], 0.f);
@@ -205,6 +284,7 @@ __device__ __forceinline__ int rayOctant(mp::Vec3 d)
 typedef float lf4 __attribute__((ext_vector_type(4)));
 typedef uint32_t lu4 __attribute__((ext_vector_type(4)));
 
+template <class LBVH>
 __device__ __forceinline__ void loadTri(const LBVH &b, int tri, mp::Vec3 &a, mp::Vec3 &bb, mp::Vec3 &c)
 {
     const MP_LDS lf4 *p = reinterpret_cast<const MP_LDS lf4 *>(b.verts) + tri * 3;
@@ -227,7 +307,7 @@ struct NodeR {
 
 __device__ __forceinline__ float qb(uint32_t w, int i) { return (float)((w >> (8 * i)) & 0xffu); }
 
-template <int kNodeQ = 4>
+template <int kNodeQ = 4, class LBVH>
 __device__ __forceinline__ NodeR loadNode(const LBVH &b, uint32_t idx)
 {
     const MP_LDS lu4 *p = reinterpret_cast<const MP_LDS lu4 *>(b.nodes) + idx * kNodeQ;
@@ -322,7 +402,8 @@ __device__ __forceinline__ bool rayTri(mp::Vec3 ta, mp::Vec3 tb, mp::Vec3 tc, co
 // the origin's components in the same order.  comp(ta - org, k) ==
 // ta[k] - org[k], so every value equals rayTri's bit for bit; per triangle
 // 6 selects replace the 18 of the per-component comp() gathers.
-__device__ __forceinline__ bool rayTriRot(const MP_LDS lf4 *p, float o0, float o1, float oz, bool sw,
+template <class VertPtr> // const MP_LDS lf4 *
+__device__ __forceinline__ bool rayTriRot(VertPtr p, float o0, float o1, float oz, bool sw,
                                           const RayTxfmD &tx, float t_max, float &out_t)
 {
     using namespace mp;
@@ -375,7 +456,7 @@ __device__ __forceinline__ bool rayTriRot(const MP_LDS lf4 *p, float o0, float o
 // kExit: stop as soon as a hit at t <= exit_at is found (t_out is then
 // that hit, not necessarily the closest; callers that only compare the
 // closest hit with exit_at get the same answer).
-template <bool kExit, int kNodeQ = 4, bool kRot = false, bool kOctImage = false>
+template <bool kExit, int kNodeQ = 4, bool kRot = false, bool kOctImage = false, class LBVH>
 __device__ __forceinline__ bool bvhTraceRayT(const LBVH &b, mp::Vec3 ray_o, mp::Vec3 ray_d, float &t_out,
                                              float t_max0, float exit_at, int *exit_tri = nullptr)
 {
@@ -409,8 +490,8 @@ __device__ __forceinline__ bool bvhTraceRayT(const LBVH &b, mp::Vec3 ray_o, mp::
 
     float t_max = t_max0;
     bool ray_hit = false;
-    ByteStack st;
-    st.lo = 0; st.hi = 0; st.n = 0;
+    typename LBVH::Stack st;
+    bsInit(st);
     bsPush(st, 0);
     while (st.n > 0) {
         const uint32_t node_idx = bsPop(st);
@@ -497,6 +578,7 @@ __device__ __forceinline__ bool bvhTraceRayT(const LBVH &b, mp::Vec3 ray_o, mp::
     return ray_hit;
 }
 
+template <class LBVH>
 __device__ __forceinline__ bool bvhTraceRayD(const LBVH &b, mp::Vec3 ray_o, mp::Vec3 ray_d, float &t_out,
                                              float t_max0 = mp::kFltMax)
 {
@@ -519,6 +601,7 @@ struct RayHitD {
     float t;
     int hit;
 };
+template <class LBVH>
 __device__ __noinline__ RayHitD bvhTraceRayExactD(const LBVH b, mp::Vec3 ray_o, mp::Vec3 ray_d)
 {
     RayHitD r;
@@ -670,6 +753,7 @@ struct SphereHit {
 // and test t_lo < fminNum(hit_t, t_exit) in child order: the same fminNum
 // over the same four values as the reference's running update (a NaN slab
 // is ignored either way; a -0 / +0 choice cannot change the < test).
+template <class LBVH>
 __device__ __forceinline__ void sNodeLoad(const LBVH &b, uint32_t node_idx, lf4 &lx, lf4 &ly, lf4 &lz, lf4 &hx, lf4 &hy,
                                           lf4 &hz, lf4 &cq, lf4 &tq)
 {
@@ -677,6 +761,7 @@ __device__ __forceinline__ void sNodeLoad(const LBVH &b, uint32_t node_idx, lf4 
     lx = q[0]; ly = q[1]; lz = q[2]; hx = q[3]; hy = q[4]; hz = q[5]; cq = q[6]; tq = q[7];
 }
 
+template <class LBVH>
 __device__ __forceinline__ SphereHit bvhSphereCastD(const LBVH b, mp::Vec3 ray_o, mp::Vec3 ray_d, float r,
                                                  float t_max0 = mp::kFltMax)
 {
@@ -694,8 +779,8 @@ __device__ __forceinline__ SphereHit bvhSphereCastD(const LBVH b, mp::Vec3 ray_o
                negZ = __builtin_signbit(inv_d.z);
     // near / far ends per axis: loR or hiR of the pre-widened node image
     // (stageBVHSphere), picked once per cast from the sign of inv_d
-    ByteStack st;
-    st.lo = 0; st.hi = 0; st.n = 0;
+    typename LBVH::Stack st;
+    bsInit(st);
     bsPush(st, 0);
     while (st.n > 0) {
         const uint32_t node_idx = bsPop(st);
@@ -759,6 +844,7 @@ __device__ __forceinline__ SphereHit bvhSphereCastD(const LBVH b, mp::Vec3 ray_o
 // cast.  act1 = false: cast 1 is not run (h1 untouched).  Inlined into its
 // one caller: 164 VGPRs and no scratch, against 168 + 48 B of spills as a
 // call (k_move -1.3%, `profiles/r04ap_lab_cast2_inline.jsonl`).
+template <class LBVH>
 __device__ __forceinline__ void bvhSphereCast2D(const LBVH b, mp::Vec3 o0, float z1, mp::Vec3 ray_d, float r,
                                              float t_max0, bool act1, SphereHit &h0, SphereHit &h1)
 {
@@ -769,15 +855,13 @@ __device__ __forceinline__ void bvhSphereCast2D(const LBVH b, mp::Vec3 o0, float
     const bool negX = __builtin_signbit(inv_d.x), negY = __builtin_signbit(inv_d.y),
                negZ = __builtin_signbit(inv_d.z);
     const Vec3 o1 = v3(o0.x, o0.y, z1);
-    ByteStack st;
-    st.lo = 0; st.hi = 0; st.n = 0;
-    uint32_t ms = 0; // 2 bits per stack entry: the casts that entered the node
-    bsPush(st, 0);
-    ms = act1 ? 3u : 1u;
+    typename LBVH::Stack st;
+    bsInit(st);
+    uint32_t ms = 0; // 2 bits per stack entry: the casts that entered the node (bsPush2)
+    bsPush2(st, ms, 0, act1 ? 3u : 1u);
     while (st.n > 0) {
-        const uint32_t node_idx = bsPop(st);
-        const uint32_t m = ms & 3u;
-        ms >>= 2;
+        uint32_t m;
+        const uint32_t node_idx = bsPop2(st, ms, m);
         lf4 lx, ly, lz, hx, hy, hz, cq, tq;
         sNodeLoad(b, node_idx, lx, ly, lz, hx, hy, hz, cq, tq);
         float lo0[4], lo1[4], ex0[4], ex1[4];
@@ -827,8 +911,7 @@ __device__ __forceinline__ void bvhSphereCast2D(const LBVH b, mp::Vec3 o0, float
                     closest1 = n1;
                 }
             } else {
-                bsPush(st, (uint32_t)child);
-                ms = (ms << 2) | pass;
+                bsPush2(st, ms, (uint32_t)child, pass);
             }
         }
     }
@@ -862,6 +945,7 @@ __device__ __forceinline__ WorldHit capsulesD(const float *__restrict__ px, cons
                                               const float *__restrict__ pz, int64_t g0, int N, mp::Vec3 org,
                                               mp::Vec3 d, int self, bool hit, float min_t, uint32_t capMask = ~0u);
 
+template <class LBVH>
 __device__ __forceinline__ WorldHit traceWorldD(const LBVH &b, const float *__restrict__ px,
                                                 const float *__restrict__ py, const float *__restrict__ pz,
                                                 int64_t g0, int N, mp::Vec3 org, mp::Vec3 d, int self = -1,
@@ -979,7 +1063,7 @@ __device__ __forceinline__ WorldHit capsulesD(const float *__restrict__ px, cons
 // runs the first part on every candidate ray and the second on the
 // unresolved ones only, compacted (the answer per ray is the same).
 // capsule(j): the base of the world's agent j's capsule (its position).
-template <class CapsuleFn>
+template <class LBVH, class CapsuleFn>
 __device__ __forceinline__ bool visibleQuickD(const LBVH &b, CapsuleFn capsule, mp::Vec3 org, mp::Vec3 d, int target,
                                               const uint16_t *occ, uint32_t numTris, float &t_c)
 {
@@ -1002,7 +1086,7 @@ __device__ __forceinline__ bool visibleQuickD(const LBVH &b, CapsuleFn capsule, 
     return false;
 }
 
-template <class CapsuleFn>
+template <class LBVH, class CapsuleFn>
 __device__ __forceinline__ bool visibleFullD(const LBVH &b, CapsuleFn capsule, int N, mp::Vec3 org, mp::Vec3 d,
                                              int target, float t_c, uint16_t *occ = nullptr)
 {
@@ -1048,6 +1132,7 @@ __device__ __forceinline__ bool visibleFullD(const LBVH &b, CapsuleFn capsule, i
     return ent == target;
 }
 
+template <class LBVH>
 __device__ __forceinline__ bool visibleRayD(const LBVH &b, const float *__restrict__ px,
                                             const float *__restrict__ py, const float *__restrict__ pz, int64_t g0,
                                             int N, mp::Vec3 org, mp::Vec3 d, int target,

@@ -462,6 +462,7 @@ __device__ __forceinline__ bool castPathQuirkFreeD(const SceneDev &sc, Vec3 o, V
 
 // The cast's hit if nearer than `near_b`, else t = kFltMax: for callers to
 // which every hit at or beyond near_b acts like no hit.  Horizontal d.
+template <class LBVH>
 __device__ __forceinline__ SphereHit castNearD(const LBVH &bvh, const SceneDev &sc, Vec3 o, Vec3 d, float near_b)
 {
     if (!castPathQuirkFreeD(sc, o, d, near_b)) return bvhSphereCastD(bvh, o, d, kSphereR);
@@ -474,6 +475,7 @@ __device__ __forceinline__ SphereHit castNearD(const LBVH &bvh, const SceneDev &
 // (o.x, o.y, z1): one traversal (bvhSphereCast2D), the same results.  The
 // path guard depends on o.xy, d and near_b only, so both casts take the
 // same branch.
+template <class LBVH>
 __device__ __forceinline__ void castNear2D(const LBVH &bvh, const SceneDev &sc, Vec3 o, float z1, Vec3 d,
                                            float near_b, bool act1, SphereHit &h0, SphereHit &h1)
 {
@@ -488,6 +490,7 @@ __device__ __forceinline__ void castNear2D(const LBVH &bvh, const SceneDev &sc, 
 
 // The full cast's t, searched within near_b first.  Vertical d only (the
 // path guard is the cell of 2o).
+template <class LBVH>
 __device__ __forceinline__ float castFirstNearD(const LBVH &bvh, const SceneDev &sc, Vec3 o, Vec3 d, float near_b)
 {
     if (castQuirkFreeD(sc, o)) {
@@ -526,6 +529,7 @@ __device__ __forceinline__ int nthSetBitD(uint64_t m, int n)
 // active lane of the wave; on small batches k_move runs 8-32 agents per
 // wave (launchMove), and round 6 deals over those lanes too (rounds 4-5 fell
 // back to the serial loop on any partial wave, i.e. always below C3).
+template <class LBVH>
 __device__ __forceinline__ void stuckCastsD(const LBVH &bvh, bool need, Vec3 x, Vec3 v_norm, float low_check,
                                             float hd4[4])
 {
@@ -565,6 +569,7 @@ __device__ __forceinline__ void stuckCastsD(const LBVH &bvh, bool need, Vec3 x, 
 // sim.cpp:889-1039 applyVelocitySystem + updateMoveStateSystem.  Split at
 // the stuck fallback so the wave can share its casts (stuckCastsD): part 1
 // up to the ground check, the fallback's casts, part 2 to the end.
+template <class LBVH>
 __device__ __forceinline__ void applyVelocityD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int64_t g)
 {
     const Vec3 x = ldPos(S, g);
@@ -694,6 +699,7 @@ __device__ __forceinline__ void applyVelocityD(const DevState &S, const SceneDev
 }
 
 // sim.cpp:1041-1104 fallSystem + updateMoveStatePostFallSystem
+template <class LBVH>
 __device__ __forceinline__ void fallD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int64_t g)
 {
     if (S.alive[g] == 0.f) return;
@@ -764,6 +770,7 @@ __device__ __forceinline__ FireIn fireLoadD(const DevState &S, int64_t g)
 // lpx / lpy / lpz, lhp, lrs: the world's agents' positions, hp and respawn
 // counters in LDS (k_sim stages them), indexed from lb (the world's first
 // lane).
+template <class LBVH>
 __device__ __forceinline__ void fireD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, int i, const FireIn &in,
                                       const float *lpx, const float *lpy, const float *lpz, const float *lhp,
                                       const float *lrs, int lb)
@@ -2666,10 +2673,11 @@ __global__ void __launch_bounds__(64) k_reset_only(DevState S, SceneDev sc)
 // apw: agents per wave (64, or fewer on small batches: a wave runs the
 // longest of its lanes' sphere-cast chains, so when the batch leaves SIMDs
 // idle, fewer agents per wave shorten every wave; launchMove picks it).
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) k_move(DevState S, SceneDev sc, int apw)
+template <class LBVH>
+__device__ __forceinline__ void moveBody(const DevState &S, const SceneDev &sc, int apw, char *img)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    LBVH bvh = stageBVHSphere(smem, sc);
+    LBVH bvh = stageBVHSphere<LBVH>(LBVH::kStaged ? smem : img, sc);
     bvh.stats = S.stats;
     [&]() {
         const int lane = threadIdx.x & 63;
@@ -2688,6 +2696,19 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))
     }();
 }
 
+// Each kernel that walks a BVH is its body instantiated over the LDS view and
+// (`_g`, with the images as one more argument) over the global one; the host
+// launcher picks by SceneImages::residency.
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) k_move(DevState S, SceneDev sc, int apw)
+{
+    moveBody<LBVHL>(S, sc, apw, nullptr);
+}
+
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) k_move_g(DevState S, SceneDev sc, int apw, SceneImages img)
+{
+    moveBody<LBVHG>(S, sc, apw, img.sphere);
+}
+
 // Step graph part 2 (fireSystem onward): per-world phases.  A workgroup
 // holds floor(kSimBlock / N) whole worlds, lane = agent, phases separated
 // by workgroup barriers.
@@ -2704,9 +2725,11 @@ constexpr size_t kSimCoopBytes = (size_t)kSimBlock * 4 * sizeof(float);
 constexpr size_t kSimReuseBytes = kSimRecOffset + kSimRecBytes;
 static_assert(kSimCoopBytes <= kSimRecOffset, "respawnCoopD's scratch must end below the spawn records");
 static_assert(kSimReuseBytes == kSimKeyBytes + kSimRecBytes, "the keys and the records are all that reuses the BVH image");
+// (kStaged: the image is in LDS; otherwise only the reused bytes are there)
+template <bool kStaged>
 __host__ __device__ size_t simSpawnOffset(const SceneDev &sc)
 {
-    const size_t bvh = (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16;
+    const size_t bvh = kStaged ? (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16 : 0;
     return ((bvh > kSimReuseBytes ? bvh : kSimReuseBytes) + 15) & ~(size_t)15;
 }
 
@@ -2735,6 +2758,7 @@ static_assert(sizeof(SimLds) == (size_t)kSimBlock * 8 * sizeof(float), "k_sim's 
 // the reset's flags are written while the world lanes still read the rewards
 static_assert(offsetof(SimRespawnLds, flags) >= sizeof(SimRewardLds), "reset flags must not overlap the rewards");
 
+template <class LBVH>
 __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, int i);
 
 // 4 waves/SIMD (128 VGPRs, at the price of ~420 B/lane of scratch spills):
@@ -2743,13 +2767,14 @@ __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev 
 #define MP_SIM_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 // flatten: every phase inlined (an outlined call needs a stack frame in
 // scratch for the whole kernel and spills around the call).
-__global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)) k_sim(DevState S, SceneDev sc)
+template <class LBVH>
+__device__ __forceinline__ __attribute__((flatten)) void simBody(const DevState &S, const SceneDev &sc, char *img)
 {
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // dynamic LDS (simLdsBytes): the BVH image, which the reset phase reuses
     // for its draw keys, then the scene's spawn lists
-    Spawn *const tabA = reinterpret_cast<Spawn *>(smem + simSpawnOffset(sc));
+    Spawn *const tabA = reinterpret_cast<Spawn *>(smem + simSpawnOffset<LBVH::kStaged>(sc));
     Spawn *const tabB = tabA + sc.numA, *const tabC = tabB + sc.numB;
     {
         const int nq = (sc.numA + sc.numB + sc.numCommon) * (int)(sizeof(Spawn) / 16);
@@ -2762,7 +2787,7 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
             dst[k] = *src;
         }
     }
-    const LBVH bvh = stageBVH(smem, sc); // (its barrier also covers the spawn lists)
+    const LBVH bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img, sc); // (its barrier also covers the spawn lists)
     // spawn records in the BVH's LDS once nothing reads the BVH any more:
     // the respawn (after fireD) unless the flank reward traces rays later,
     // the reset (last phase) unless curriculum snapshots rewrite agents after
@@ -2984,6 +3009,16 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
     }
 }
 
+__global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)) k_sim(DevState S, SceneDev sc)
+{
+    simBody<LBVHL>(S, sc, nullptr);
+}
+
+__global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)) k_sim_g(DevState S, SceneDev sc, SceneImages img)
+{
+    simBody<LBVHG>(S, sc, img.sphere);
+}
+
 // utils.cpp:169-184 inFrustum
 __device__ __forceinline__ bool inFrustumD(const SceneDev &sc, Vec3 vp)
 {
@@ -3026,6 +3061,7 @@ __device__ __forceinline__ Vec3 visSamplePointD(const DevState &S, int64_t gt, V
 
 // utils.cpp:169-271 isAgentVisible for one (viewer, target) pair, lane-wise
 // (the flank reward's checks; k_vis batches the opponent checks instead).
+template <class LBVH>
 __device__ __forceinline__ bool isAgentVisibleD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, Vec3 org,
                                 Quat aim_rot, int target)
 {
@@ -3051,6 +3087,7 @@ __device__ __forceinline__ bool isAgentVisibleD(const DevState &S, const SceneDe
 // opponent that cannot see the agent (judged with the agent's own aim),
 // hits / kills from behind the target, exploration.  CombatState is taken
 // by value there, so nothing is cleared.
+template <class LBVH>
 __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, int i)
 {
     const int T = S.T, N = S.N;
@@ -3091,7 +3128,8 @@ __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev 
     return r;
 }
 
-__global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
+template <class LBVH>
+__device__ __forceinline__ void visBody(const DevState &S, const SceneDev &sc, char *img)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ uint16_t rays[kVisMaxRays];  // (lane << 2) | point
@@ -3109,7 +3147,7 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
     const int64_t wave = ((int64_t)xcdBlockId() * blockDim.x + threadIdx.x) >> 6;
     const int64_t agent0 = (((int64_t)xcdBlockId() * blockDim.x) >> 6) * apw; // first agent of the block
     const int nsMax = visStageAgents(T, N);
-    float *st = (float *)(smem + (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16);
+    float *st = (float *)(smem + (LBVH::kStaged ? (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16 : 0));
     const int64_t s0 = (agent0 / N) * N;
     {
         const int64_t a_hi = min(S.A, agent0 + (int64_t)(kBlock / 64) * apw);
@@ -3131,7 +3169,7 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
     // tree): which triangles a traversal reaches depends on the tree for rays
     // along a zero-margin child box face, so another tree can answer
     // differently (DESIGN.md section 2 definition 4).  Barrier.
-    const LBVH bvh = stageBVH(smem, sc);
+    const LBVH bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img, sc);
     auto sPos = [&](int64_t g) {
         const int l = (int)(g - s0);
         return v3(st[0 * nsMax + l], st[1 * nsMax + l], st[2 * nsMax + l]);
@@ -3277,6 +3315,16 @@ __global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
         const bool valid = wl < apw * T && g < S.A;
         if (valid && wl % T == 0) S.visMask[g] = (uint8_t)masks[(int)(g - agent0)];
     }
+}
+
+__global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
+{
+    visBody<LBVHL>(S, sc, nullptr);
+}
+
+__global__ void __launch_bounds__(kBlock) k_vis_g(DevState S, SceneDev sc, SceneImages img)
+{
+    visBody<LBVHG>(S, sc, img.sphere);
 }
 
 __device__ __forceinline__ Vec3 normalizedPosD(const SceneDev &sc, Vec3 p) // sim.cpp:2693-2718
@@ -3959,7 +4007,8 @@ __device__ __forceinline__ int rowMaxBits16(int v)
     return max(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false)); // row_ror:8
 }
 
-__global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S, SceneDev sc, int iters)
+template <class LBVH>
+__device__ __forceinline__ void lidarBody(const DevState &S, const SceneDev &sc, int iters, char *img)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // Ray-fan directions (sim.cpp:3324-3506): theta depends only on the ray
@@ -4030,7 +4079,7 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
     // ever waits for another.  With one task per wave nothing is drawn.
     __shared__ uint32_t nextTask;
     if (threadIdx.x == 0) nextTask = kLidarWaves;
-    const LBVH bvh = stageBVHOct(smem, sc); // ends with __syncthreads
+    const LBVH bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img, sc); // ends with __syncthreads
     auto draw = [&]() {
         if (iters == 1) return (uint32_t)kLidarWaves;
         // the lane id read here (volatile, as in the loop body): hoisted out
@@ -4264,15 +4313,36 @@ __global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S,
     }
 }
 
+__global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S, SceneDev sc, int iters)
+{
+    lidarBody<LBVHL>(S, sc, iters, nullptr);
+}
+
+__global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar_g(DevState S, SceneDev sc, int iters, SceneImages img)
+{
+    lidarBody<LBVHG>(S, sc, iters, img.oct);
+}
+
+// The global-resident images, once per scene upload: one block runs the
+// staging loops of stageBVHSphere (whose image begins with stageBVH's) and
+// stageBVHOct into the two buffers, so the bytes are those a block of the
+// LDS path stages for itself.
+__global__ void __launch_bounds__(kBlock) k_scene_images(SceneDev sc, SceneImages img)
+{
+    (void)stageBVHSphere<LBVHG, true>(img.sphere, sc);
+    (void)stageBVHOct<LBVHG, true>(img.oct, sc);
+}
+
 static int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
 
 // Debug/test hook: closest-hit BVH queries for caller rays (mode 0 = the
 // traversal inlined into the step kernels, 1 = its out-of-line copy).
-__global__ void __launch_bounds__(kBlock) k_trace_rays(SceneDev sc, const float *o, const float *d, int n, int mode,
-                                                       float *t_out, int32_t *hit_out)
+template <class LBVH>
+__device__ __forceinline__ void traceRaysBody(const SceneDev &sc, const float *o, const float *d, int n, int mode,
+                                              float *t_out, int32_t *hit_out, char *img)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const LBVH bvh = stageBVH(smem, sc);
+    const LBVH bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img, sc);
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const Vec3 org = v3(o[3 * r], o[3 * r + 1], o[3 * r + 2]);
@@ -4290,30 +4360,48 @@ __global__ void __launch_bounds__(kBlock) k_trace_rays(SceneDev sc, const float 
     hit_out[r] = hit ? 1 : 0;
 }
 
-int launchTraceRays(const SceneDev &sc, const float *o, const float *d, int n, int mode, float *t, int32_t *hit,
-                    void *stream)
+__global__ void __launch_bounds__(kBlock) k_trace_rays(SceneDev sc, const float *o, const float *d, int n, int mode,
+                                                       float *t_out, int32_t *hit_out)
+{
+    traceRaysBody<LBVHL>(sc, o, d, n, mode, t_out, hit_out, nullptr);
+}
+
+__global__ void __launch_bounds__(kBlock) k_trace_rays_g(SceneDev sc, const float *o, const float *d, int n, int mode,
+                                                         float *t_out, int32_t *hit_out, SceneImages img)
+{
+    traceRaysBody<LBVHG>(sc, o, d, n, mode, t_out, hit_out, img.sphere);
+}
+
+int launchTraceRays(const SceneDev &sc, const SceneImages &img, const float *o, const float *d, int n, int mode,
+                    float *t, int32_t *hit, void *stream)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(k_trace_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), bvhLdsBytes(sc),
-                       (hipStream_t)stream, sc, o, d, n, mode, t, hit);
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(k_trace_rays_g, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, sc,
+                           o, d, n, mode, t, hit, img);
+    else
+        hipLaunchKernelGGL(k_trace_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), bvhLdsBytes(sc),
+                           (hipStream_t)stream, sc, o, d, n, mode, t, hit);
     return check(hipGetLastError());
 }
 
 // Test hook (mpenv_debug_geom_queries, include/mpenv.h): one geometry query
-// per thread through the step kernels' own device functions, on the LDS image
-// of the kernel each mode stands in for (k_lidar / k_sim / k_vis / k_move).
+// per thread through the step kernels' own device functions, on the image
+// (LDS- or global-resident, as the step kernels' own) of the kernel each mode
+// stands in for (k_lidar / k_sim / k_vis / k_move).
 // The functions are force-inlined, so this is a second compilation of them:
 // it checks their shortcut arguments on chosen inputs, not the step kernels'
 // code generation (whole-step parity covers that).
-template <int kMode>
-__global__ void __launch_bounds__(kBlock) k_geom_queries(SceneDev sc, mpenv_geom_queries q, int n)
+template <int kMode, class LBVH>
+__device__ __forceinline__ void geomQueriesBody(const SceneDev &sc, const mpenv_geom_queries &q, int n,
+                                                const SceneImages &img)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LBVH bvh;
-    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) bvh = stageBVHOct(smem, sc);
-    else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) bvh = stageBVH(smem, sc);
-    else if constexpr (kMode == MPENV_GEOM_SIGHT) bvh = stageBVH(smem, sc);
-    else bvh = stageBVHSphere(smem, sc);
+    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img.oct, sc);
+    else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
+    else if constexpr (kMode == MPENV_GEOM_SIGHT) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
+    else bvh = stageBVHSphere<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const Vec3 org = v3(q.o[3 * r], q.o[3 * r + 1], q.o[3 * r + 2]);
@@ -4393,11 +4481,46 @@ __global__ void __launch_bounds__(kBlock) k_geom_queries(SceneDev sc, mpenv_geom
     }
 }
 
-int launchGeomQueries(const SceneDev &sc, int mode, int n, const mpenv_geom_queries &q, void *stream)
+template <int kMode>
+__global__ void __launch_bounds__(kBlock) k_geom_queries(SceneDev sc, mpenv_geom_queries q, int n)
+{
+    geomQueriesBody<kMode, LBVHL>(sc, q, n, SceneImages {});
+}
+
+template <int kMode>
+__global__ void __launch_bounds__(kBlock) k_geom_queries_g(SceneDev sc, mpenv_geom_queries q, int n, SceneImages img)
+{
+    geomQueriesBody<kMode, LBVHG>(sc, q, n, img);
+}
+
+int launchGeomQueries(const SceneDev &sc, const SceneImages &img, int mode, int n, const mpenv_geom_queries &q,
+                      void *stream)
 {
     if (n <= 0) return 0;
     const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
+    if (img.residency == kResidencyGlobal) {
+        switch (mode) {
+        case MPENV_GEOM_LIDAR_RAY:
+            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_LIDAR_RAY>, grid, block, 0, st, sc, q, n, img);
+            break;
+        case MPENV_GEOM_WORLD_RAY:
+            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_WORLD_RAY>, grid, block, 0, st, sc, q, n, img);
+            break;
+        case MPENV_GEOM_SIGHT:
+            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_SIGHT>, grid, block, 0, st, sc, q, n, img);
+            break;
+        case MPENV_GEOM_CASTS:
+            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_CASTS>, grid, block, 0, st, sc, q, n, img);
+            break;
+        case MPENV_GEOM_STUCK:
+            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_STUCK>, grid, block, 0, st, sc, q, n, img);
+            break;
+        default:
+            return -1;
+        }
+        return check(hipGetLastError());
+    }
     switch (mode) {
     case MPENV_GEOM_LIDAR_RAY:
         hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_LIDAR_RAY>, grid, block, bvhLdsBytesOct(sc), st, sc, q, n);
@@ -4569,9 +4692,38 @@ const char *kernelName(int k)
 
 size_t bvhLdsBytes(const SceneDev &sc) { return (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16; }
 
-size_t simLdsBytes(const SceneDev &sc)
+// The step kernels' dynamic LDS under a residency: global-resident, only
+// what a kernel keeps beside the image is left.
+size_t simLdsBytes(const SceneDev &sc, int32_t residency)
 {
-    return simSpawnOffset(sc) + (size_t)(sc.numA + sc.numB + sc.numCommon) * sizeof(Spawn);
+    const size_t off = residency == kResidencyGlobal ? simSpawnOffset<false>(sc) : simSpawnOffset<true>(sc);
+    return off + (size_t)(sc.numA + sc.numB + sc.numCommon) * sizeof(Spawn);
+}
+
+size_t moveLdsBytes(const SceneDev &sc, int32_t residency)
+{
+    return residency == kResidencyGlobal ? 0 : bvhLdsBytesSphere(sc);
+}
+
+size_t visLdsBytes(const SceneDev &sc, int32_t residency, int T)
+{
+    size_t stage = 0;
+    for (int t = T > 0 ? T : 1; t <= (T > 0 ? T : kMaxTeamSize); t++)
+        stage = std::max(stage, (size_t)kVisStageCols * 4 * visStageAgents(t, 2 * t));
+    return (residency == kResidencyGlobal ? 0 : bvhLdsBytes(sc)) + stage;
+}
+
+size_t lidarLdsBytes(const SceneDev &sc, int32_t residency)
+{
+    return residency == kResidencyGlobal ? 0 : bvhLdsBytesOct(sc);
+}
+
+int buildSceneImages(const SceneDev &sc, const SceneImages &img, void *stream)
+{
+    hipLaunchKernelGGL(k_scene_images, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, sc, img);
+    int rc = check(hipGetLastError());
+    if (!rc) rc = check(hipStreamSynchronize((hipStream_t)stream));
+    return rc;
 }
 static_assert(c::kAgentRadius == kSphereR, "k_move sphere casts use the agent radius (stageBVHSphere)");
 
@@ -4602,7 +4754,7 @@ int launchResetOnly(const DevState &s, const SceneDev &sc, void *stream)
     return check(hipGetLastError());
 }
 
-int launchMove(const DevState &s, const SceneDev &sc, void *stream)
+int launchMove(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
 {
     // Small batches (< 64 full blocks): one-wave blocks, so the few waves spread over CUs
     // instead of sharing a CU's SIMDs (k_move is latency-bound: 5-7
@@ -4615,26 +4767,39 @@ int launchMove(const DevState &s, const SceneDev &sc, void *stream)
     const int64_t waves = (s.A + apw - 1) / apw;
     const int bs = waves < 64 * 4 ? 64 : kBlock;
     const int64_t threads = waves * 64;
-    hipLaunchKernelGGL(k_move, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), bvhLdsBytesSphere(sc),
-                       (hipStream_t)stream, s, sc, apw);
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(k_move_g, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, s,
+                           sc, apw, img);
+    else
+        hipLaunchKernelGGL(k_move, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), bvhLdsBytesSphere(sc),
+                           (hipStream_t)stream, s, sc, apw);
     return check(hipGetLastError());
 }
 
-int launchSimStep(const DevState &s, const SceneDev &sc, void *stream)
+int launchSimStep(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
 {
     const int wpb = kSimBlock / s.N;
     const int blocks = (s.W + wpb - 1) / wpb;
-    hipLaunchKernelGGL(k_sim, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc), (hipStream_t)stream, s, sc);
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(k_sim_g, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, kResidencyGlobal),
+                           (hipStream_t)stream, s, sc, img);
+    else
+        hipLaunchKernelGGL(k_sim, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, kResidencyLds), (hipStream_t)stream,
+                           s, sc);
     return check(hipGetLastError());
 }
 
-int launchVisibility(const DevState &s, const SceneDev &sc, void *stream)
+int launchVisibility(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
 {
     const int64_t waves = (s.A + (64 / s.T) - 1) / (64 / s.T);
     const int blocks = (int)((waves * 64 + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_vis, dim3(blocks), dim3(kBlock),
-                       bvhLdsBytes(sc) + (size_t)kVisStageCols * 4 * visStageAgents(s.T, s.N),
-                       (hipStream_t)stream, s, sc);
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(k_vis_g, dim3(blocks), dim3(kBlock), visLdsBytes(sc, kResidencyGlobal, s.T),
+                           (hipStream_t)stream, s, sc, img);
+    else
+        hipLaunchKernelGGL(k_vis, dim3(blocks), dim3(kBlock),
+                           bvhLdsBytes(sc) + (size_t)kVisStageCols * 4 * visStageAgents(s.T, s.N),
+                           (hipStream_t)stream, s, sc);
     return check(hipGetLastError());
 }
 
@@ -4682,14 +4847,17 @@ int lidarItersFor(int64_t A)
     return (int)std::max<int64_t>(1, std::min<int64_t>(kLidarItersAuto, lidarTasks(A) / (kLidarWaves * 1024)));
 }
 
-int launchLidar(const DevState &s, const SceneDev &sc, int iters, void *stream)
+int launchLidar(const DevState &s, const SceneDev &sc, const SceneImages &img, int iters, void *stream)
 {
     if (iters < 1 || iters > kLidarIters) return -1; // the agent stage is sized for kLidarIters
     const int64_t tasks = lidarTasks(s.A);
     const int64_t per_block = (int64_t)kLidarWaves * iters;
     const int blocks = (int)((tasks + per_block - 1) / per_block);
-    hipLaunchKernelGGL(k_lidar, dim3(blocks), dim3(kLidarBlock), bvhLdsBytesOct(sc), (hipStream_t)stream, s, sc,
-                       iters);
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(k_lidar_g, dim3(blocks), dim3(kLidarBlock), 0, (hipStream_t)stream, s, sc, iters, img);
+    else
+        hipLaunchKernelGGL(k_lidar, dim3(blocks), dim3(kLidarBlock), bvhLdsBytesOct(sc), (hipStream_t)stream, s, sc,
+                           iters);
     return check(hipGetLastError());
 }
 

@@ -154,25 +154,25 @@ void mpenv_manager::record(hipStream_t st)
 void mpenv_manager::stepRange(const DevState &R, const SceneDev &rsc, hipStream_t st)
 {
     record(st);
-    launched(launchMove(R, rsc, st), "k_move launch failed");
+    launched(launchMove(R, rsc, img, st), "k_move launch failed");
     record(st);
-    launched(launchSimStep(R, rsc, st), "k_sim launch failed");
+    launched(launchSimStep(R, rsc, img, st), "k_sim launch failed");
     record(st);
     if (lidarBranch && groups == 1 && !timing) {
         HIP_CHECK(hipEventRecord(bForkEv, st));
         bSide.startAfter(bForkEv);
-        launched(launchLidar(R, rsc, lidarItersOf(R), bSide.stream), "k_lidar launch failed");
+        launched(launchLidar(R, rsc, img, lidarItersOf(R), bSide.stream), "k_lidar launch failed");
         bSide.markDone();
-        launched(launchVisibility(R, rsc, st), "k_vis launch failed");
+        launched(launchVisibility(R, rsc, img, st), "k_vis launch failed");
         launched(launchObservations(R, rsc, st), "k_obs launch failed");
         bSide.joinInto(st);
         return;
     }
-    launched(launchVisibility(R, rsc, st), "k_vis launch failed");
+    launched(launchVisibility(R, rsc, img, st), "k_vis launch failed");
     record(st);
     launched(launchObservations(R, rsc, st), "k_obs launch failed");
     record(st);
-    launched(launchLidar(R, rsc, lidarItersOf(R), st), "k_lidar launch failed");
+    launched(launchLidar(R, rsc, img, lidarItersOf(R), st), "k_lidar launch failed");
     record(st);
 }
 
@@ -235,6 +235,7 @@ std::vector<char> mpenv_manager::argKey() const
     put(&lidarIters, sizeof(lidarIters));
     put(&S, sizeof(S));
     put(&sc, sizeof(sc));
+    put(&img, sizeof(img));
     for (const DevState &G : gS) put(&G, sizeof(G));
     for (const SceneDev &g : gsc) put(&g, sizeof(g));
     return k;
@@ -331,9 +332,9 @@ void mpenv_manager::runInitGraph(hipStream_t st)
     // (sim.cpp:5322-5340): resetSystem + observations + lidar.
     HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)S.reset, 1, (size_t)S.W, st));
     launched(launchResetOnly(S, sc, st), "k_reset launch failed");
-    launched(launchVisibility(S, sc, st), "k_vis launch failed");
+    launched(launchVisibility(S, sc, img, st), "k_vis launch failed");
     launched(launchObservations(S, sc, st), "k_obs launch failed");
-    launched(launchLidar(S, sc, lidarItersOf(S), st), "k_lidar launch failed");
+    launched(launchLidar(S, sc, img, lidarItersOf(S), st), "k_lidar launch failed");
 }
 
 template <typename T>
@@ -635,6 +636,8 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
         // matching the synchronous Manager::step contract (mgr.cpp:1949-1960).
         m->stream = Stream::create(hipStreamDefault);
         m->scene = loadScene(m->scenePath, (cfg->sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
+        m->limits = sceneLimits(m->scene);
+        if (!m->limits.supported) return fail(MPENV_ERR_UNSUPPORTED, "scene not supported: " + m->limits.reason);
         buildSceneDev(*m);
         m->S.W = (int32_t)cfg->num_worlds;
         m->S.T = (int32_t)cfg->team_size;
@@ -664,6 +667,14 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
             int want = 1;
             if (const char *e = std::getenv("MPENV_WORLD_GROUPS")) want = std::atoi(e);
             m->setupGroups(want);
+        }
+        if (const char *e = std::getenv("MPENV_SCENE_RESIDENCY")) {
+            const std::string v = e;
+            const int32_t mode = v == "auto" ? MPENV_SCENE_AUTO : v == "lds" ? MPENV_SCENE_LDS
+                                 : v == "global"                             ? MPENV_SCENE_GLOBAL
+                                                                             : -1;
+            if (mpenv_set_scene_residency(m.get(), mode) != MPENV_OK)
+                throw std::runtime_error("MPENV_SCENE_RESIDENCY=" + v + ": " + g_last_error);
         }
         if (const char *e = std::getenv("MPENV_STEP_GRAPH")) m->useGraph = std::atoi(e) != 0;
         if (const char *e = std::getenv("MPENV_LIDAR_BRANCH"))
@@ -906,7 +917,7 @@ int mpenv_debug_trace_rays(mpenv_manager *m, const float *o, const float *d, int
 {
     if (!m || !o || !d || !t_out || !hit_out || n < 0) return fail(MPENV_ERR_INVALID, "bad argument");
     hipStream_t st = streamOf(m, stream);
-    if (launchTraceRays(m->sc, o, d, n, mode, t_out, hit_out, st) || hipStreamSynchronize(st) != hipSuccess)
+    if (launchTraceRays(m->sc, m->img, o, d, n, mode, t_out, hit_out, st) || hipStreamSynchronize(st) != hipSuccess)
         return fail(MPENV_ERR_HIP, "trace-ray launch failed");
     return MPENV_OK;
 }
@@ -926,7 +937,7 @@ int mpenv_debug_geom_queries(mpenv_manager *m, int32_t mode, int32_t n, const mp
     if (mode == MPENV_GEOM_STUCK) ok = ok && q->sel && q->bound && n % 64 == 0;
     if (!ok) return fail(MPENV_ERR_INVALID, "bad geometry query");
     hipStream_t st = streamOf(m, stream);
-    if (launchGeomQueries(m->sc, mode, n, *q, st) || hipStreamSynchronize(st) != hipSuccess)
+    if (launchGeomQueries(m->sc, m->img, mode, n, *q, st) || hipStreamSynchronize(st) != hipSuccess)
         return fail(MPENV_ERR_HIP, "geometry-query launch failed");
     return MPENV_OK;
 }
@@ -1421,6 +1432,31 @@ int mpenv_set_world_groups(mpenv_manager *m, int32_t groups)
         HIP_CHECK(hipStreamSynchronize(m->stream));
         m->setupGroups(groups);
     });
+}
+
+int mpenv_set_scene_residency(mpenv_manager *m, int32_t mode)
+{
+    if (!m) return fail(MPENV_ERR_INVALID, "null manager");
+    if (mode != MPENV_SCENE_AUTO && mode != MPENV_SCENE_LDS && mode != MPENV_SCENE_GLOBAL)
+        return fail(MPENV_ERR_INVALID, "scene residency must be MPENV_SCENE_AUTO, MPENV_SCENE_LDS or MPENV_SCENE_GLOBAL "
+                                       "(MPENV_SCENE_RESIDENCY=auto|lds|global)");
+    if (mode == MPENV_SCENE_LDS && !m->limits.ldsOk)
+        return fail(MPENV_ERR_INVALID, "scene does not fit the LDS-resident path: " + m->limits.ldsWhyNot);
+    return guarded([&] {
+        // the kernels of a step in flight keep the path they were launched
+        // on; the step graph is keyed on m->img (argKey) and re-captured
+        HIP_CHECK(hipStreamSynchronize(m->stream));
+        m->residencyMode = mode;
+        const bool lds = mode == MPENV_SCENE_LDS || (mode == MPENV_SCENE_AUTO && m->limits.ldsOk);
+        m->img.residency = lds ? kResidencyLds : kResidencyGlobal;
+    });
+}
+
+int mpenv_scene_residency(mpenv_manager *m, int32_t *mode_in_use)
+{
+    if (!m || !mode_in_use) return fail(MPENV_ERR_INVALID, "null argument");
+    *mode_in_use = m->img.residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+    return MPENV_OK;
 }
 
 int mpenv_world_groups(mpenv_manager *m, int32_t *groups)

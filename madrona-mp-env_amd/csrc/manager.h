@@ -26,6 +26,18 @@ int fail(int code, const std::string &msg);
 // manager_scene.cpp: the scene's device image (m.sc and its buffers) from
 // m.scene and m.cfg.
 void buildSceneDev(mpenv_manager &m);
+// manager_scene.cpp: which residency a scene can have -- the one place that
+// decides it, for mpenv_create, mpenv_set_scene_residency and mpenv_scene_info.
+struct SceneLimits {
+    int32_t tris = 0, lidarTris = 0, nodes = 0, lidarNodes = 0, stack = 0, lidarStack = 0;
+    size_t ldsMove = 0, ldsSim = 0, ldsVis = 0, ldsLidar = 0; // dynamic LDS asked for on the LDS path
+    size_t globalBytes = 0;                                     // the global-resident images
+    bool ldsOk = false;     // meets every limit of the LDS-resident path
+    bool supported = false; // by one path at least
+    std::string ldsWhyNot;  // the first LDS limit missed
+    std::string reason;     // !supported: why
+};
+SceneLimits sceneLimits(const Scene &s);
 } // namespace mpenv
 
 #define HIP_CHECK(expr)                                                                   \
@@ -162,6 +174,11 @@ struct mpenv_manager {
     int gpu = 0;
     Scene scene;
     SceneDev sc;
+    // the global-resident images and the path in use (manager_scene.cpp);
+    // part of the step graph's key
+    SceneImages img {};
+    int32_t residencyMode = MPENV_SCENE_AUTO; // as asked for
+    SceneLimits limits;
     DevState S;
     Stream stream;
     std::vector<void *> allocations;

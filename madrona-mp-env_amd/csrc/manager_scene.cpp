@@ -27,6 +27,21 @@ void navTriVerts(const NavMesh &nm, float *out)
         }
 }
 
+// The counts the LDS-size functions of engine.h read, without device pointers.
+SceneDev sceneCounts(const Scene &s)
+{
+    SceneDev sc;
+    std::memset(&sc, 0, sizeof(sc));
+    sc.numNodes = (int32_t)s.nodes.size();
+    sc.numVerts = (int32_t)s.bvhVerts.size();
+    sc.numLidarNodes = (int32_t)s.lidarNodes.size();
+    sc.numLidarVerts = (int32_t)s.lidarVerts.size();
+    sc.numA = (int32_t)s.aSpawns.size();
+    sc.numB = (int32_t)s.bSpawns.size();
+    sc.numCommon = (int32_t)s.commonRespawns.size();
+    return sc;
+}
+
 // A BVH query's answer: the counts always, nodes and vertices where the
 // caller's buffer is there and its capacity (the count passed in) suffices.
 void bvhOut(const std::vector<BVHNode> &nodes, const std::vector<mp::Vec3> &verts, int32_t maxStack, void *nodes_out,
@@ -46,16 +61,55 @@ void bvhOut(const std::vector<BVHNode> &nodes, const std::vector<mp::Vec3> &vert
 
 } // namespace
 
+// Path selection.  LDS-resident: node indices fit the byte stack's entries,
+// the stack bounds its 16 entries, and each step kernel's dynamic LDS request
+// the 64 KB a block gets without a function attribute.  Global-resident: the
+// stack bounds fit the WideStack (as many entries as the oracle's stack), the
+// triangles k_vis's 16-bit occluder hints, and what k_sim and k_vis still
+// keep in LDS the same 64 KB.
+SceneLimits mpenv::sceneLimits(const Scene &s)
+{
+    SceneLimits l;
+    l.tris = (int32_t)(s.bvhVerts.size() / 3);
+    l.lidarTris = (int32_t)(s.lidarVerts.size() / 3);
+    l.nodes = (int32_t)s.nodes.size();
+    l.lidarNodes = (int32_t)s.lidarNodes.size();
+    l.stack = std::max(s.maxStack, s.maxStackAnyOrder);
+    l.lidarStack = s.lidarMaxStack;
+    const SceneDev sc = sceneCounts(s);
+    l.ldsMove = moveLdsBytes(sc, kResidencyLds);
+    l.ldsSim = simLdsBytes(sc, kResidencyLds);
+    l.ldsVis = visLdsBytes(sc, kResidencyLds, 0);
+    l.ldsLidar = lidarLdsBytes(sc, kResidencyLds);
+    l.globalBytes = bvhLdsBytesSphere(sc) + bvhLdsBytesOct(sc);
+    auto num = [](size_t v) { return std::to_string(v); };
+    if (l.nodes > kMaxLdsNodes) l.ldsWhyNot = "collision BVH has " + num(l.nodes) + " nodes (byte stack: 256)";
+    else if (l.lidarNodes > kMaxLdsNodes) l.ldsWhyNot = "lidar BVH has " + num(l.lidarNodes) + " nodes (byte stack: 256)";
+    else if (l.stack > kMaxBVHStack) l.ldsWhyNot = "collision BVH stack bound " + num(l.stack) + " (register stack: 16)";
+    else if (l.lidarStack > kMaxBVHStack) l.ldsWhyNot = "lidar BVH stack bound " + num(l.lidarStack) + " (register stack: 16)";
+    else if (l.ldsMove > kLdsBudget) l.ldsWhyNot = "k_move would ask for " + num(l.ldsMove) + " B of LDS (64 KB)";
+    else if (l.ldsSim > kLdsBudget) l.ldsWhyNot = "k_sim would ask for " + num(l.ldsSim) + " B of LDS (64 KB)";
+    else if (l.ldsVis > kLdsBudget) l.ldsWhyNot = "k_vis would ask for " + num(l.ldsVis) + " B of LDS (64 KB)";
+    else if (l.ldsLidar > kLdsBudget) l.ldsWhyNot = "k_lidar would ask for " + num(l.ldsLidar) + " B of LDS (64 KB)";
+    l.ldsOk = l.ldsWhyNot.empty();
+    if (l.tris > kMaxSceneTris)
+        l.reason = num(l.tris) + " collision triangles (k_vis's 16-bit occluder hints: " + num(kMaxSceneTris) + ")";
+    else if (l.stack > kMaxGlobalStack)
+        l.reason = "collision BVH stack bound " + num(l.stack) + " (traversal stack: " + num(kMaxGlobalStack) + ")";
+    else if (l.lidarStack > kMaxGlobalStack)
+        l.reason = "lidar BVH stack bound " + num(l.lidarStack) + " (traversal stack: " + num(kMaxGlobalStack) + ")";
+    else if (!l.ldsOk && simLdsBytes(sc, kResidencyGlobal) > kLdsBudget)
+        l.reason = "spawn lists need " + num(simLdsBytes(sc, kResidencyGlobal)) + " B of k_sim's LDS (64 KB)";
+    l.supported = l.reason.empty();
+    return l;
+}
+
 void mpenv::buildSceneDev(mpenv_manager &m)
 {
     Scene &s = m.scene;
     SceneDev &sc = m.sc;
     std::memset(&sc, 0, sizeof(sc));
-    if (s.nodes.size() > 256) throw std::runtime_error("BVH has more than 256 nodes (byte-stack limit)");
-    if (s.maxStack > kMaxBVHStack || s.maxStackAnyOrder > kMaxBVHStack)
-        throw std::runtime_error("BVH too deep for the 16-entry register stack");
-    if (s.lidarNodes.size() > 256) throw std::runtime_error("lidar BVH has more than 256 nodes (byte-stack limit)");
-    if (s.lidarMaxStack > kMaxBVHStack) throw std::runtime_error("lidar BVH too deep for the 16-entry register stack");
+    if (!m.limits.supported) throw std::runtime_error("scene not supported: " + m.limits.reason);
     if (s.zoneAABBs.empty() || s.zoneAABBs.size() > (size_t)kMaxZones) throw std::runtime_error("bad zone count");
     if (s.numDefaultASpawns == 0 || s.numDefaultBSpawns == 0) throw std::runtime_error("scene needs A and B spawns");
     if ((m.cfg.sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) &&
@@ -229,6 +283,14 @@ void mpenv::buildSceneDev(mpenv_manager &m)
         launched(computeSceneFrames(d_tab, m.stream), "k_scene_frames launch failed");
         sc.tab = d_tab;
     }
+    {
+        // the global-resident images, whichever path is in use: switching
+        // residency later allocates nothing
+        m.img.sphere = m.alloc<char>(bvhLdsBytesSphere(sc));
+        m.img.oct = m.alloc<char>(bvhLdsBytesOct(sc));
+        m.img.residency = m.limits.ldsOk ? kResidencyLds : kResidencyGlobal;
+        launched(buildSceneImages(sc, m.img, m.stream), "k_scene_images launch failed");
+    }
     sc.simFlags = m.cfg.sim_flags;
     sc.autoReset = m.cfg.auto_reset;
     sc.worldOffset = m.cfg.world_id_offset;
@@ -272,6 +334,29 @@ int mpenv_scene_quirk_grid(const char *scene_path, int32_t *header_out, uint32_t
         }
         if (bits_out && *num_words >= (int32_t)q.bits.size()) std::memcpy(bits_out, q.bits.data(), q.bits.size() * 4);
         *num_words = (int32_t)q.bits.size();
+    }, MPENV_ERR_IO);
+}
+
+int mpenv_scene_info(const char *scene_path, mpenv_scene_info_t *out)
+{
+    if (!scene_path || !out) return fail(MPENV_ERR_INVALID, "null argument");
+    return guarded([&] {
+        const SceneLimits l = sceneLimits(loadScene(scene_path));
+        std::memset(out, 0, sizeof(*out));
+        out->triangles = l.tris;
+        out->collision_nodes = l.nodes;
+        out->collision_stack = l.stack;
+        out->lidar_nodes = l.lidarNodes;
+        out->lidar_stack = l.lidarStack;
+        out->lidar_triangles = l.lidarTris;
+        out->supported = l.supported ? 1 : 0;
+        out->residency = !l.supported ? MPENV_SCENE_AUTO : l.ldsOk ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+        out->lds_bytes_move = (int64_t)l.ldsMove;
+        out->lds_bytes_sim = (int64_t)l.ldsSim;
+        out->lds_bytes_vis = (int64_t)l.ldsVis;
+        out->lds_bytes_lidar = (int64_t)l.ldsLidar;
+        out->global_bytes = (int64_t)l.globalBytes;
+        std::snprintf(out->reason, sizeof(out->reason), "%s", l.supported ? l.ldsWhyNot.c_str() : l.reason.c_str());
     }, MPENV_ERR_IO);
 }
 

@@ -358,6 +358,19 @@ PYBIND11_MODULE(madrona_mp_env, m)
             return e;
         })
         .def("set_world_groups", [](PySimManager &s, int32_t g) { check(mpenv_set_world_groups(s.h->mgr, g)); })
+        // "auto", "lds" or "global" (mpenv_scene_residency.h); "lds" on a scene that does not fit raises
+        .def("set_scene_residency", [](PySimManager &s, const std::string &name) {
+            const int32_t mode = name == "auto" ? MPENV_SCENE_AUTO : name == "lds" ? MPENV_SCENE_LDS
+                                 : name == "global"                               ? MPENV_SCENE_GLOBAL
+                                                                                  : -1;
+            check(mpenv_set_scene_residency(s.h->mgr, mode));
+        }, py::arg("residency"))
+        // the path in use: "lds" or "global"
+        .def("scene_residency", [](PySimManager &s) {
+            int32_t mode = 0;
+            check(mpenv_scene_residency(s.h->mgr, &mode));
+            return std::string(mode == MPENV_SCENE_LDS ? "lds" : "global");
+        })
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
         .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
         .def("graph_status", [](PySimManager &s) {
@@ -503,6 +516,26 @@ PYBIND11_MODULE(madrona_mp_env, m)
     // row_bytes, row_kind, export_id, dtype, dims); dims are the export's for
     // an exported section, else (rows, elements per row).  idx -1: the blob.
     // mpenv_policy_check: validates a converted-checkpoint directory (no manager, no GPU)
+    // what a scene directory asks of the engine (mpenv_scene_residency.h); no GPU, no manager
+    m.def("scene_info", [](const std::string &path) {
+        mpenv_scene_info_t i;
+        check(mpenv_scene_info(path.c_str(), &i));
+        py::dict d;
+        d["triangles"] = i.triangles;
+        d["collision_nodes"] = i.collision_nodes;
+        d["collision_stack"] = i.collision_stack;
+        d["lidar_nodes"] = i.lidar_nodes;
+        d["lidar_stack"] = i.lidar_stack;
+        d["lidar_triangles"] = i.lidar_triangles;
+        d["lds_bytes"] = py::dict(py::arg("k_move") = i.lds_bytes_move, py::arg("k_sim") = i.lds_bytes_sim,
+                                  py::arg("k_vis") = i.lds_bytes_vis, py::arg("k_lidar") = i.lds_bytes_lidar);
+        d["global_bytes"] = i.global_bytes;
+        d["residency"] = !i.supported ? py::object(py::none())
+                                      : py::object(py::str(i.residency == MPENV_SCENE_LDS ? "lds" : "global"));
+        d["supported"] = i.supported != 0;
+        d["reason"] = std::string(i.reason);
+        return d;
+    }, py::arg("path"));
     m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;
