@@ -454,7 +454,7 @@ int mpenv_debug_trace_rays(mpenv_manager *mgr, const float *o_device, const floa
 /* Test hook (no reference counterpart): the device geometry queries of the
  * step kernels, one query per thread over caller buffers in device memory.
  * The kernel calls the step kernels' own device functions (geom_dev.h and
- * the cast wrappers of kernels.hip) on an LDS image staged by the same
+ * the cast wrappers of casts_dev.h) on an LDS image staged by the same
  * staging function, with the same LDS size, as the kernel it stands in for.
  * It proves the shortcut arguments of those functions (bounded searches,
  * early exits, hints, culls, shared traversals, dealt casts) on inputs a

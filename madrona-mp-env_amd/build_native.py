@@ -12,6 +12,7 @@ import os
 import subprocess
 import sys
 import sysconfig
+from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -26,11 +27,11 @@ LIB = os.path.join(PKG, "libmpenv.so")
 EXT = os.path.join(PKG, "madrona_mp_env" + sysconfig.get_config_var("EXT_SUFFIX"))
 ORACLE_LIB = os.path.join(ORACLE, "_build", "liboracle.so")
 
-LIB_SOURCES = ["kernels.hip", "wire.hip", "state.hip", "policy.hip", "manager.cpp", "manager_scene.cpp", "policy.cpp",
-               "scene.cpp", "navmesh.cpp"]
-LIB_HEADERS = ["mpenv_core.h", "engine.h", "geom_dev.h", "scene.h", "policy.h", "manager.h"]
+LIB_SOURCES = ["kernels.hip", "move.hip", "vis.hip", "obs.hip", "lidar.hip", "hooks.hip", "wire.hip", "state.hip",
+               "policy.hip", "manager.cpp", "manager_scene.cpp", "policy.cpp", "scene.cpp", "navmesh.cpp"]
 API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h", "mpenv_policy_precision.h",
                                                      "mpenv_scene_residency.h")]
+MAX_PARALLEL = 16  # what one command may use on the GPU machines, whatever the machine's CPU count
 
 
 def _stale(out, deps):
@@ -46,28 +47,59 @@ def _run(cmd):
     subprocess.run(cmd, check=True, stdout=sys.stderr)
 
 
-def build_lib(force=False):
-    srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in LIB_HEADERS] + API_HEADERS
-    if not force and not _stale(LIB, deps):
-        return LIB
-    objdir = os.path.join(PKG, "build")
+def compile_flags(src_dir, extra=()):
+    """The flags every translation unit of libmpenv.so is compiled with."""
+    return ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{src_dir}", f"-I{INCLUDE}",
+            "-Wall", "-Wno-unused-variable", "-Wno-unused-function"] + list(extra)
+
+
+def compile_cmd(src, out, src_dir, extra=(), mode=("-c",)):
+    """hipcc line for one of LIB_SOURCES; `mode` is what to emit (-c, -S, -fsyntax-only ...),
+    `out` None for a mode that writes no file."""
+    to = ["-o", out] if out else []
+    if src.endswith(".hip"):
+        return [HIPCC, "-x", "hip", f"--offload-arch={ARCH}", *mode, src] + to + compile_flags(src_dir, extra)
+    return ([HIPCC, "-x", "c++", *mode, src] + to + compile_flags(src_dir, extra) +
+            ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"])
+
+
+def _compile(cmd):
+    # one print per unit, command and compiler output together, so concurrent units do not interleave
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    print("[build] " + " ".join(cmd) + "\n" + r.stdout, end="", file=sys.stderr, flush=True)
+    return r.returncode
+
+
+def compile_and_link(src_dir, objdir, out, extra=(), force=True):
+    """The one compile recipe: LIB_SOURCES of `src_dir` into objects under
+    `objdir`, concurrently, then linked into the shared library `out`.
+    force=False recompiles only the objects older than their source or any
+    header, and relinks when an object is newer than the library."""
+    headers = [os.path.join(src_dir, h) for h in sorted(os.listdir(src_dir)) if h.endswith(".h")] + API_HEADERS
+    srcs = [os.path.join(src_dir, s) for s in LIB_SOURCES]
+    objs = [os.path.join(objdir, s + ".o") for s in LIB_SOURCES]
+    if not force and not _stale(out, srcs + headers + [o for o in objs if os.path.exists(o)]):
+        return out  # up to date, with or without its objects (a tree may travel without them)
     os.makedirs(objdir, exist_ok=True)
-    objs = []
-    common = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-              f"-I{CSRC}", f"-I{INCLUDE}", "-Wall", "-Wno-unused-variable",
-              "-Wno-unused-function"]
-    for s in srcs:
-        o = os.path.join(objdir, os.path.basename(s) + ".o")
-        if s.endswith(".hip"):
-            cmd = [HIPCC, "-x", "hip", f"--offload-arch={ARCH}", "-c", s, "-o", o] + common
-        else:
-            cmd = [HIPCC, "-x", "c++", "-c", s, "-o", o] + common + ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        _run(cmd)
-        objs.append(o)
-    _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs +
-         ["-Wl,-soname,libmpenv.so"])
-    return LIB
+    todo = [compile_cmd(src, o, src_dir, extra) for src, o in zip(srcs, objs)
+            if force or _stale(o, [src] + headers)]
+    if todo:
+        jobs = max(1, min(MAX_PARALLEL, int(os.environ.get("MAX_JOBS") or MAX_PARALLEL), len(todo)))
+        with ThreadPoolExecutor(jobs) as pool:
+            codes = list(pool.map(_compile, todo))
+        failed = [cmd for cmd, rc in zip(todo, codes) if rc]
+        if failed:
+            # last, below every unit's output: which units failed
+            for cmd in failed:
+                print("[build] FAILED:", next(a for a in cmd if a.endswith((".hip", ".cpp"))), file=sys.stderr, flush=True)
+            raise subprocess.CalledProcessError(1, failed[0])
+    if todo or _stale(out, objs):
+        _run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", out] + objs + ["-Wl,-soname,libmpenv.so"])
+    return out
+
+
+def build_lib(force=False):
+    return compile_and_link(CSRC, os.path.join(PKG, "build"), LIB, force=force)
 
 
 def build_ext(force=False):

@@ -368,13 +368,8 @@ struct SceneImages {
     int32_t residency;
 };
 
-// Host launchers (kernels.hip)
-struct LaunchCtx {
-    void *stream;       // hipStream_t
-    void *events[16];   // optional per-kernel timing events (start/stop pairs)
-    int timing;         // record events when nonzero
-};
-
+// Host launchers: each in the file of its kernel (move, vis, obs, lidar, hooks;
+// k_sim's, the scene upload's and the action kernels' in kernels.hip)
 enum KernelId { kKMove = 0, kKSim = 1, kKVis = 2, kKObs = 3, kKLidar = 4, kNumTimedKernels = 5 };
 
 const char *kernelName(int k);

@@ -5,9 +5,11 @@
 // NVRTC megakernel).  Every dependency between those systems is *within a
 // world* (SURVEY.md §8e), so here a workgroup owns a tile of worlds and the
 // system chain becomes LDS/L1-local __syncthreads() barriers.  The step is
-// four kernels:
+// five kernels, k_sim here and the others in a file each (move.hip, vis.hip,
+// obs.hip, lidar.hip):
 //
-//   k_sim    world tile, lane = agent: movement + sphere casts, fire, damage,
+//   k_move   lane = agent: bots, movement + sphere casts, aim, fall
+//   k_sim    world tile, lane = agent: fire, damage,
 //            respawn, heal, zone, breadcrumbs, match info, goals, explore,
 //            rewards, done, reset  (sim.cpp:5347-5841 up to resetSystem)
 //   k_vis    lane = (agent, opponent): frustum + line-of-sight rays
@@ -19,189 +21,14 @@
 // All traversals read an LDS-resident copy of the BVH (geom_dev.h).  Every
 // arithmetic expression follows the reference (and the CPU oracle) term by
 // term with -ffp-contract=off so that results are bit-identical.
-#include <hip/hip_runtime.h>
-
-#include "engine.h"
-#include "geom_dev.h"
+#include "nav_dev.h"
+#include "sight_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace mpenv {
 
 using namespace mp;
-
-// ----------------------------------------------------- consts.hpp:7-72
-namespace c {
-constexpr int kNumStepsPerZone = 600;
-constexpr int kZonePointInterval = 20;
-constexpr int kZoneWinPoints = 125;
-constexpr int kPoseTransitionSpeed = 10;
-constexpr float kAgentRadius = 15.f;
-constexpr float kStandHeight = 65.f;
-constexpr float kCrouchHeight = 47.f;
-constexpr float kProneHeight = 30.f;
-constexpr float kMaxRunVelocity = 400.f;
-constexpr float kMaxWalkVelocity = 200.f;
-constexpr float kMaxCrouchVelocity = 50.f;
-constexpr float kMaxProneVelocity = 20.f;
-constexpr float kDeaccelerateRate = 1000.f;
-constexpr int kRespawnInvincibleSteps = 5;
-constexpr int kOutOfCombatSteps = 150;
-constexpr float kAutohealPerStep = 5.f;
-constexpr int kEpisodeLen = 3000;
-constexpr int kNumMoveAmountBuckets = 3;
-constexpr int kNumMoveAngleBuckets = 8;
-constexpr float kDeltaT = 0.05f;
-constexpr int kDiscreteAimYawBuckets = 13;
-constexpr int kDiscreteAimPitchBuckets = 7;
-constexpr int kGridMax = 40;
-// mgr.cpp:1383-1395 weapon stats
-constexpr int kMagSize = 30;
-constexpr int kReloadTime = 30;
-constexpr float kDmgPerBullet = 10.f;
-constexpr float kAccuracyScale = 0.005f;
-constexpr int kNumWeaponTypes = 1;
-} // namespace c
-
-enum { kStand = 0, kCrouch = 1, kProne = 2 };
-constexpr uint32_t kFlagNoRespawn = 1u << 3;
-constexpr uint32_t kFlagSpawnInMiddle = 1u << 0;
-constexpr uint32_t kFlagRandomizeHP = 1u << 1;
-constexpr uint32_t kFlagHardcodedSpawns = 1u << 6;
-constexpr uint32_t kFlagEnableCurriculum = 1u << 5;
-constexpr uint32_t kFlagNavmeshSpawn = 1u << 2;
-constexpr uint32_t kFlagSubZones = 1u << 11;
-
-__device__ __forceinline__ float viewHeightD(int pose)
-{
-    float top = pose == kStand ? c::kStandHeight : (pose == kCrouch ? c::kCrouchHeight : c::kProneHeight);
-    return top - c::kAgentRadius;
-}
-
-__device__ __forceinline__ int32_t f2iSatD(float f)
-{
-    if (!(f == f)) return 0;
-    if (f >= 2147483520.f) return INT32_MAX;
-    if (f <= -2147483648.f) return INT32_MIN;
-    return (int32_t)f;
-}
-
-// ------------------------------------------------------ SoA accessors
-__device__ __forceinline__ Vec3 ldPos(const DevState &S, int64_t g) { return v3(S.px[g], S.py[g], S.pz[g]); }
-__device__ __forceinline__ void stPos(const DevState &S, int64_t g, Vec3 p) { S.px[g] = p.x; S.py[g] = p.y; S.pz[g] = p.z; }
-__device__ __forceinline__ Vec3 ldVel(const DevState &S, int64_t g) { return v3(S.vx[g], S.vy[g], S.vz[g]); }
-__device__ __forceinline__ void stVel(const DevState &S, int64_t g, Vec3 v) { S.vx[g] = v.x; S.vy[g] = v.y; S.vz[g] = v.z; }
-__device__ __forceinline__ Quat ldRot(const DevState &S, int64_t g) { return quat(S.rw[g], S.rx[g], S.ry[g], S.rz[g]); }
-__device__ __forceinline__ void stRot(const DevState &S, int64_t g, Quat q) { S.rw[g] = q.w; S.rx[g] = q.x; S.ry[g] = q.y; S.rz[g] = q.z; }
-__device__ __forceinline__ Quat ldAimRot(const DevState &S, int64_t g) { return quat(S.aw[g], S.ax[g], S.ay[g], S.az[g]); }
-__device__ __forceinline__ void stAimRot(const DevState &S, int64_t g, Quat q) { S.aw[g] = q.w; S.ax[g] = q.x; S.ay[g] = q.y; S.az[g] = q.z; }
-__device__ __forceinline__ RNG ldRng(const DevState &S, int64_t g)
-{
-    RNG r; r.key.a = (uint32_t)S.rngA[g]; r.key.b = (uint32_t)S.rngB[g]; r.ctr = (uint32_t)S.rngCtr[g];
-    return r;
-}
-__device__ __forceinline__ void stRng(const DevState &S, int64_t g, const RNG &r)
-{
-    S.rngA[g] = (int32_t)r.key.a; S.rngB[g] = (int32_t)r.key.b; S.rngCtr[g] = (int32_t)r.ctr;
-}
-__device__ __forceinline__ RNG ldWRng(const DevState &S, int w)
-{
-    RNG r; r.key.a = (uint32_t)S.wRngA[w]; r.key.b = (uint32_t)S.wRngB[w]; r.ctr = (uint32_t)S.wRngCtr[w];
-    return r;
-}
-__device__ __forceinline__ void stWRng(const DevState &S, int w, const RNG &r)
-{
-    S.wRngA[w] = (int32_t)r.key.a; S.wRngB[w] = (int32_t)r.key.b; S.wRngCtr[w] = (int32_t)r.ctr;
-}
-__device__ __forceinline__ void setFlag(const DevState &S, int64_t g, int32_t bit, bool v)
-{
-    int32_t f = S.flags[g];
-    S.flags[g] = v ? (f | bit) : (f & ~bit);
-}
-
-struct AimD {
-    float yaw, pitch;
-    Quat rot;
-};
-
-// utils.cpp:140-167 computeAim
-__device__ __forceinline__ AimD computeAimD(float yaw, float pitch)
-{
-    if (yaw < -kPi) yaw += 2.f * kPi;
-    else if (yaw > kPi) yaw -= 2.f * kPi;
-    if (pitch < -0.25f * kPi) pitch = -0.25f * kPi;
-    if (pitch > 0.25f * kPi) pitch = 0.25f * kPi;
-    Quat r = angleAxis(yaw, kUp) * angleAxis(pitch, kRight);
-    r = qnormalize(r);
-    AimD a;
-    a.yaw = yaw; a.pitch = pitch; a.rot = r;
-    return a;
-}
-
-__device__ __forceinline__ void stAim(const DevState &S, int64_t g, const AimD &a)
-{
-    S.ayaw[g] = a.yaw; S.apitch[g] = a.pitch; stAimRot(S, g, a.rot);
-}
-
-// ====================================================== per-agent systems
-// sim.cpp:2057-2091 applyBotActionsSystem
-// ---- scripted bots: NavUtils (sim.cpp:4958-5037) + planAStarAISystem
-// (sim.cpp:5041-5172).  The triangle loops index the navmesh uniformly
-// across the wave, so its vertices come in as scalar loads.
-__device__ __forceinline__ Vec3 navVertD(const SceneDev &sc, int tri, int k)
-{
-    const float *p = sc.navTris + 9 * tri + 3 * k;
-    return v3(p[0], p[1], p[2]);
-}
-
-__device__ Vec3 navTriCenterD(const SceneDev &sc, int tri)
-{
-    Vec3 c = v3(0.f, 0.f, 0.f);
-    for (int k = 0; k < 3; k++) c = c + navVertD(sc, tri, k) / 3.0f;
-    return c;
-}
-
-// NearestNavTri (sim.cpp:4975-5010): first containing triangle (xy winding
-// test), else the candidate kept by the reference's distance bookkeeping.
-__device__ int nearestNavTriD(const SceneDev &sc, Vec3 pos)
-{
-    float closest = kFltMax;
-    int closest_idx = -1;
-    for (int tri = 0; tri < sc.numNavTris; tri++) {
-        bool contained = true;
-        bool gtz = false;
-        for (int k = 0; k < 3; k++) {
-            const Vec3 v1 = navVertD(sc, tri, k);
-            const Vec3 v2 = navVertD(sc, tri, k == 2 ? 0 : k + 1);
-            const Vec3 e = v2 - v1;
-            const Vec3 vp = pos - v1;
-            const Vec3 c = cross(e, vp);
-            if ((c.z > 0.0f) != gtz && k > 0) contained = false;
-            gtz = c.z > 0.0f;
-            float distsq = length2(v1 - pos);
-            if (distsq < closest) {
-                const float dir = dot(e, vp);
-                const Vec3 perp = vp * (-dir / dot(e, e)) + e;
-                distsq = dot(perp, perp);
-                if (distsq < closest) {
-                    closest = fabs_(c.z);
-                    closest_idx = tri;
-                }
-            }
-        }
-        if (contained) return tri;
-    }
-    return closest_idx;
-}
-
-__device__ __forceinline__ FrameDev makeFrameD(Vec3 pmin, Vec3 pmax, float rot)
-{
-    FrameDev f;
-    f.toFrame = qinv(angleAxis(rot, kUp));
-    f.pMin = rotateVec(f.toFrame, pmin);
-    f.pMax = rotateVec(f.toFrame, pmax);
-    return f;
-}
 
 // Zone and goal-region frames, once at scene upload (see FrameDev).
 __global__ void k_scene_frames(SceneTables *tab)
@@ -225,496 +52,6 @@ __global__ void k_zone_goals(SceneDev sc, int32_t *out)
     const AABB z = sc.zoneAABB[zi];
     const Vec3 center = (z.pMin + z.pMax) / 2.f; // as planAStarD forms it
     out[zi] = nearestNavTriD(sc, center);
-}
-
-// PathfindToPoint (sim.cpp:5012-5035); goal_tri = NearestNavTri(pos)
-__device__ Vec3 pathfindToPointD(const SceneDev &sc, Vec3 start, Vec3 pos, int goal_tri)
-{
-    const int start_tri = nearestNavTriD(sc, start);
-    if (start_tri < 0 || goal_tri < 0) return v3(0.f, 0.f, 0.f); // (asserted in the reference)
-    const int next = sc.astar[start_tri * sc.numNavTris + goal_tri];
-    if (next == -1) return v3(0.f, 0.f, 0.f);
-    if (next == goal_tri) return pos;
-    return navTriCenterD(sc, next);
-}
-
-__device__ __forceinline__ void planAStarD(const DevState &S, const SceneDev &sc, int64_t g)
-{
-    if (S.policy[g] != -1) return; // consts::aStarPolicyID
-    const int w = (int)(g / S.N);
-    RNG rng = ldRng(S, g);
-    int move_amount = rngI32(rng, 0, 2);
-    int move_angle = rngI32(rng, 0, 2);
-    int r_yaw = rngI32(rng, 0, 5);
-    const int r_pitch = rngI32(rng, 0, 2);
-    const int reload = S.magazine[2 * g] == 0 ? 1 : 0;
-    int stand = rngI32(rng, 0, 2);
-    stRng(S, g, rng);
-    // fire if any opponent is visible (OpponentsVisibility of the last step)
-    int fire = (S.visMask[g] & ((1u << S.T) - 1u)) != 0 ? 1 : 0;
-
-    const int zi = S.curZone[w];
-    const AABB z = sc.tab->zoneAABB[zi];
-    Vec3 center = (z.pMin + z.pMax) / 2.f; // AABB::centroid
-    const Vec3 pos = v3(S.px[g], S.py[g], 0.f);
-    center = pathfindToPointD(sc, pos, center, sc.tab->zoneGoalTri[zi]);
-    center.z = 0.f;
-    const float yaw = S.ayaw[g];
-    const Vec3 fwd = v3(-sinf_(yaw), cosf_(yaw), 0.f);
-    const Vec3 tgt = normalize(center - pos);
-    move_amount = dot(fwd, tgt) > 0.6f ? 1 : 0;
-    r_yaw = cross(fwd, tgt).z < 0.0f ? 0 + move_amount : 4 - move_amount;
-    move_amount *= 2;
-    move_angle = 0;
-    stand = 0;
-
-    // wall avoidance from last step's forward lidar depths
-    float coll_ang = 0.f, coll_norm = 0.f;
-    const float *lid = &S.fwdLidar[g * kFwdRays * 4];
-    for (int y = 0; y < 2; y++) {
-        for (int x = 0; x < 32; x++) {
-            if (lid[(y * 32 + x) * 4] < 16.0f) {
-                coll_norm++;
-                coll_ang += x;
-            }
-        }
-    }
-    if (coll_norm > 0.f) {
-        coll_ang /= coll_norm;
-        move_amount = 1;
-        switch ((int)(coll_ang / 32.f * 8.0f)) {
-        case 0: move_angle = 2; break;
-        case 1:
-        case 2: move_angle = 3; break;
-        case 3:
-        case 4: move_angle = 4; move_amount = 2; break;
-        case 5:
-        case 6: move_angle = 5; break;
-        case 7: move_angle = 6; break;
-        }
-    }
-    if (reload) fire = 0;
-    if (fire) r_yaw = 2;
-    int32_t *out = &S.botAction[7 * g];
-    out[0] = move_amount;
-    out[1] = move_angle;
-    out[2] = r_yaw;
-    out[3] = r_pitch;
-    out[4] = fire;
-    out[5] = reload;
-    out[6] = stand;
-}
-
-__device__ __forceinline__ void applyBotActionsD(const DevState &S, int64_t g)
-{
-    if (S.policy[g] != -1) return;
-    const int32_t *hb = &S.botAction[7 * g];
-    S.discreteAction[4 * g + 0] = hb[0];
-    S.discreteAction[4 * g + 1] = hb[1];
-    S.discreteAction[4 * g + 2] = hb[4];
-    S.discreteAction[4 * g + 3] = hb[6];
-    const float turn_delta = 10.f / (float)(5 / 2);
-    S.aimAction[2 * g] = turn_delta * (float)(hb[2] - 5 / 2);
-    S.aimAction[2 * g + 1] = turn_delta * (float)(hb[3] - 5 / 2);
-}
-
-// sim.cpp:2093-2199 pvpMovementSystem
-__device__ __forceinline__ void pvpMovementD(const DevState &S, int64_t g)
-{
-    if (S.alive[g] == 0.f) return;
-    const int32_t a_amount = S.discreteAction[4 * g + 0];
-    const int32_t a_angle = S.discreteAction[4 * g + 1];
-    const int32_t a_stand = S.discreteAction[4 * g + 3];
-    Vec3 vel = ldVel(S, g);
-    {
-        float v_len = length(vel);
-        if (v_len > 0.f) {
-            Vec3 norm_v = vel / v_len;
-            v_len -= c::kDeaccelerateRate * c::kDeltaT;
-            v_len = fmaxD(0.f, v_len);
-            vel = norm_v * v_len;
-        }
-    }
-    int cur = S.curPose[g], tgt = S.tgtPose[g], tr = S.transRem[g];
-    if (tr > 0) {
-        tr -= 1;
-        if (tr == 0) cur = tgt;
-    }
-    if (a_stand != tgt) {
-        tgt = a_stand;
-        int dst = tgt - cur;
-        dst = dst < 0 ? -dst : dst;
-        tr = dst * (c::kPoseTransitionSpeed / 2);
-    }
-    S.curPose[g] = cur; S.tgtPose[g] = tgt; S.transRem[g] = tr;
-
-    float accel_max = 3000;
-    if (cur == kCrouch) accel_max = 100;
-    else if (cur == kProne) accel_max = 50;
-    float move_amount = (float)a_amount * (accel_max / (float)(c::kNumMoveAmountBuckets - 1));
-    const float per_bucket = 2.f * kPi / float(c::kNumMoveAngleBuckets);
-    float move_angle = float(a_angle) * per_bucket;
-    float f_x = move_amount * sinf_(move_angle);
-    float f_y = move_amount * cosf_(move_angle);
-    vel = vel + rotateVec(ldRot(S, g), v3(f_x, f_y, 0)) * c::kDeltaT;
-    if (move_amount != 0) S.respawnSteps[g] = 0;
-    float v_len = length(vel);
-    if (v_len == 0.f) {
-        stVel(S, g, vel);
-        return;
-    }
-    float max_vel = S.maxVel[g];
-    {
-        const float max_change = 510.f;
-        float tgt_v;
-        if (cur == kStand) tgt_v = a_amount == 2 ? c::kMaxRunVelocity : c::kMaxWalkVelocity;
-        else if (cur == kCrouch) tgt_v = c::kMaxCrouchVelocity;
-        else tgt_v = c::kMaxProneVelocity;
-        float diff = tgt_v - max_vel;
-        float adj = fmaxD(fminD(diff, max_change), -max_change);
-        max_vel += adj;
-    }
-    S.maxVel[g] = max_vel;
-    Vec3 v_norm = vel / v_len;
-    v_len = fminD(v_len, max_vel);
-    stVel(S, g, v_norm * v_len);
-}
-
-// sim.cpp:2266-2370 continuous then discrete aim
-__device__ __forceinline__ void pvpAimD(const DevState &S, int64_t g)
-{
-    if (S.alive[g] == 0.f) return;
-    float yaw = S.ayaw[g], pitch = S.apitch[g];
-    yaw += S.aimAction[2 * g] * c::kDeltaT;
-    pitch += S.aimAction[2 * g + 1] * c::kDeltaT;
-    AimD a = computeAimD(yaw, pitch);
-    yaw = a.yaw; pitch = a.pitch;
-    // pvpContinuousAimSystem writes Rotation too; it is overwritten below.
-    const float yaw_turn[7] = { 0, 0.00390625f * kPi, 0.0078125f * kPi, 0.015625f * kPi,
-                                0.03125f * kPi, 0.0625f * kPi, 0.125f * kPi };
-    const float pitch_turn[4] = { 0, 0.0078125f * kPi, 0.015625f * kPi, 0.03125f * kPi };
-    int yb = S.discreteAim[2 * g] - c::kDiscreteAimYawBuckets / 2;
-    int yba = yb < 0 ? -yb : yb;
-    if (yb < 0) yaw -= yaw_turn[yba];
-    else yaw += yaw_turn[yba];
-    int pb = S.discreteAim[2 * g + 1] - c::kDiscreteAimPitchBuckets / 2;
-    int pba = pb < 0 ? -pb : pb;
-    if (pb < 0) pitch -= pitch_turn[pba];
-    else pitch += pitch_turn[pba];
-    a = computeAimD(yaw, pitch);
-    stAim(S, g, a);
-    stRot(S, g, qnormalize(angleAxis(a.yaw, kUp)));
-}
-
-__device__ __forceinline__ Vec3 rotate2DD(Vec3 dir, float radians) // sim.cpp:874-879
-{
-    float cc = cosf_(radians);
-    float s = sinf_(radians);
-    return v3(cc * dir.x - s * dir.y, s * dir.x + cc * dir.y, 0);
-}
-
-// Distance-bounded sphere casts (k_move).  MeshBVH::sphereCast prunes boxes
-// beyond its current hit, so with t_max = B it visits the same boxes in the
-// same order as the unbounded cast minus those entered beyond B, and
-// returns the same hit and normal whenever the unbounded cast's hit is
-// nearer than B -- except through the vertex-test quirk (scene.h
-// quirkGrid): testVert tests the ray 2o + t·d against a sphere of radius r
-// around each vertex, so a visited triangle with a vertex within r of that
-// ray at some t < B returns t (0 when 2o itself is inside) although the
-// geometry is far away; a bounded cast may never visit that triangle.  A
-// bounded cast is therefore only used when every grid cell under the xy
-// path 2o .. 2o + B·d is clear (each clear cell is farther than r + 2 from
-// every vertex); otherwise, and where the caller needs more than "hit
-// nearer than B or not", the full cast runs.  Vertical casts have a
-// one-cell path.  DESIGN.md §2.
-// Bound = the largest distance the caller compares a hit with + this slack
-// (a bounded miss then reads as a hit that far away, well past every
-// comparison, whatever the rounding).
-constexpr float kCastSlack = 4.f;
-
-__device__ __forceinline__ bool castQuirkFreeD(const SceneDev &sc, Vec3 o)
-{
-    const float fx = ((o.x + o.x) - sc.qgMinX) * sc.qgInvCell;
-    const float fy = ((o.y + o.y) - sc.qgMinY) * sc.qgInvCell;
-    if (!(fx >= 0.f && fx < (float)sc.qgW && fy >= 0.f && fy < (float)sc.qgH)) return true;
-    const uint32_t bit = (uint32_t)(int)fy * (uint32_t)sc.qgW + (uint32_t)(int)fx;
-    return !((sc.quirkGrid[bit >> 5] >> (bit & 31)) & 1u);
-}
-
-// Every cell of the xy bounding box of the segment 2o .. 2o + B·d is clear
-// (cells outside the grid are clear by construction: the grid reaches
-// r + margin + one cell beyond every vertex).
-__device__ __forceinline__ bool castPathQuirkFreeD(const SceneDev &sc, Vec3 o, Vec3 d, float B)
-{
-    const float px = o.x + o.x, py = o.y + o.y;
-    const float qx = px + d.x * B, qy = py + d.y * B;
-    const int x0 = max((int)floorf((fminf(px, qx) - sc.qgMinX) * sc.qgInvCell), 0);
-    const int x1 = min((int)floorf((fmaxf(px, qx) - sc.qgMinX) * sc.qgInvCell), sc.qgW - 1);
-    const int y0 = max((int)floorf((fminf(py, qy) - sc.qgMinY) * sc.qgInvCell), 0);
-    const int y1 = min((int)floorf((fmaxf(py, qy) - sc.qgMinY) * sc.qgInvCell), sc.qgH - 1);
-    for (int y = y0; y <= y1; y++)
-        for (int x = x0; x <= x1; x++) {
-            const uint32_t bit = (uint32_t)y * (uint32_t)sc.qgW + (uint32_t)x;
-            if ((sc.quirkGrid[bit >> 5] >> (bit & 31)) & 1u) return false;
-        }
-    return true;
-}
-
-// The cast's hit if nearer than `near_b`, else t = kFltMax: for callers to
-// which every hit at or beyond near_b acts like no hit.  Horizontal d.
-template <class LBVH>
-__device__ __forceinline__ SphereHit castNearD(const LBVH &bvh, const SceneDev &sc, Vec3 o, Vec3 d, float near_b)
-{
-    if (!castPathQuirkFreeD(sc, o, d, near_b)) return bvhSphereCastD(bvh, o, d, kSphereR);
-    SphereHit h = bvhSphereCastD(bvh, o, d, kSphereR, near_b);
-    if (!(h.t < near_b)) h.t = kFltMax;
-    return h;
-}
-
-// castNearD for the low cast from o and, when act1, the high cast from
-// (o.x, o.y, z1): one traversal (bvhSphereCast2D), the same results.  The
-// path guard depends on o.xy, d and near_b only, so both casts take the
-// same branch.
-template <class LBVH>
-__device__ __forceinline__ void castNear2D(const LBVH &bvh, const SceneDev &sc, Vec3 o, float z1, Vec3 d,
-                                           float near_b, bool act1, SphereHit &h0, SphereHit &h1)
-{
-    if (!castPathQuirkFreeD(sc, o, d, near_b)) {
-        bvhSphereCast2D(bvh, o, z1, d, kSphereR, kFltMax, act1, h0, h1);
-        return;
-    }
-    bvhSphereCast2D(bvh, o, z1, d, kSphereR, near_b, act1, h0, h1);
-    if (!(h0.t < near_b)) h0.t = kFltMax;
-    if (act1 && !(h1.t < near_b)) h1.t = kFltMax;
-}
-
-// The full cast's t, searched within near_b first.  Vertical d only (the
-// path guard is the cell of 2o).
-template <class LBVH>
-__device__ __forceinline__ float castFirstNearD(const LBVH &bvh, const SceneDev &sc, Vec3 o, Vec3 d, float near_b)
-{
-    if (castQuirkFreeD(sc, o)) {
-        const float t = bvhSphereCastD(bvh, o, d, kSphereR, near_b).t;
-        if (t < near_b) return t;
-    }
-    return bvhSphereCastD(bvh, o, d, kSphereR).t;
-}
-
-// Index of the n-th set bit (0-based) of m; m has more than n set bits.
-__device__ __forceinline__ int nthSetBitD(uint64_t m, int n)
-{
-    int pos = 0;
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) {
-        const uint64_t low = m & ((1ull << w) - 1ull);
-        const int c = __popcll(low);
-        if (n >= c) {
-            n -= c;
-            m >>= w;
-            pos += w;
-        } else {
-            m = low;
-        }
-    }
-    return pos;
-}
-
-// The "stuck" fallback's four horizontal casts (sim.cpp:962-984), for the
-// lanes of the wave with `need` set: their 4·k casts are dealt one per
-// active lane across the wave (rounds of as many casts as the wave has
-// active lanes) instead of four in a row on the owning lane -- a wave holding
-// one stuck agent runs one cast's time, not four.  Each cast is the same
-// function of the same owner inputs (x, v_norm, low_check shuffled from the
-// owner), so hd4 is bit-identical to the serial loop's.  Called by every
-// active lane of the wave; on small batches k_move runs 8-32 agents per
-// wave (launchMove), and round 6 deals over those lanes too (rounds 4-5 fell
-// back to the serial loop on any partial wave, i.e. always below C3).
-template <class LBVH>
-__device__ __forceinline__ void stuckCastsD(const LBVH &bvh, bool need, Vec3 x, Vec3 v_norm, float low_check,
-                                            float hd4[4])
-{
-    const float r = c::kAgentRadius;
-    const uint64_t act = __ballot(1);
-    const uint64_t m = __ballot(need);
-    if (m == 0ull) return;
-    const int na = __popcll(act);
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const int arank = __popcll(act & ((1ull << lane) - 1ull)); // this lane's index among the active lanes
-    const int rank = __popcll(m & ((1ull << lane) - 1ull));    // owner's index among the stuck lanes
-    const int tasks = 4 * __popcll(m);
-    for (int base = 0; base < tasks; base += na) {
-        const int t = base + arank;
-        const int owner = nthSetBitD(m, min(t, tasks - 1) >> 2);
-        const float ox = __shfl(x.x, owner), oy = __shfl(x.y, owner), oz = __shfl(x.z, owner);
-        const float vx = __shfl(v_norm.x, owner), vy = __shfl(v_norm.y, owner), vz = __shfl(v_norm.z, owner);
-        const float lc = __shfl(low_check, owner);
-        float hd = 0.f;
-        if (t < tasks) {
-            const Vec3 dv = rotate2DD(v3(vx, vy, vz), (float)(t & 3) * 3.14159f * 0.5f);
-            Vec3 ray_o = v3(ox, oy, oz) - dv * r * 2.0f;
-            ray_o.z += lc;
-            hd = bvhSphereCastD(bvh, ray_o, dv, r).t;
-        }
-#pragma unroll
-        for (int dir = 0; dir < 4; dir++) {
-            const int tt = 4 * rank + dir;
-            // the active lane that ran task tt this round (any lane when none did)
-            const int src = nthSetBitD(act, min(max(tt - base, 0), na - 1));
-            const float got = __shfl(hd, src);
-            if (need && tt >= base && tt < base + na) hd4[dir] = got;
-        }
-    }
-}
-
-// sim.cpp:889-1039 applyVelocitySystem + updateMoveStateSystem.  Split at
-// the stuck fallback so the wave can share its casts (stuckCastsD): part 1
-// up to the ground check, the fallback's casts, part 2 to the end.
-template <class LBVH>
-__device__ __forceinline__ void applyVelocityD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int64_t g)
-{
-    const Vec3 x = ldPos(S, g);
-    Vec3 v = ldVel(S, g);
-    v.z = 0;
-    Vec3 new_pos = x;
-    Vec3 new_vel = v3(0.f, 0.f, 0.f);
-    const int pose = S.curPose[g];
-    float v_len = length(v);
-    const float buffer = 0.05f * c::kAgentRadius;
-    const float r = c::kAgentRadius;
-    float top = c::kStandHeight - r;
-    float low_check = c::kProneHeight;
-    if (pose == kCrouch) {
-        top = c::kCrouchHeight - r;
-    } else if (pose == kProne) {
-        top = low_check;
-        low_check = c::kProneHeight - r + buffer;
-    }
-    Vec3 v_norm = v3(0.f, 0.f, 0.f);
-    Vec3 hit_pos = x, ground_check = x;
-    float ground_dist = 0.f;
-    bool cont = false, stuck_path = false;
-    do {
-        if (v_len == 0.f) break;
-        v_norm = v / v_len;
-        float move_dist = v_len * c::kDeltaT;
-
-        Vec3 ray_o = x;
-        ray_o.z += top;
-        Vec3 normal = v3(0.f, 0.f, 0.f);
-        {
-            // the ground below, wherever it is (a bounded first try gains
-            // nothing here: the downward cast prunes at the floor anyway)
-            SphereHit h = bvhSphereCastD(bvh, ray_o, -kUp, r);
-            if (h.t < kFltMax) normal = h.n;
-        }
-        if (normal.z > 0.0f && (double)normal.z < 0.7 && dot(normal, v_norm) < 0.0f) break;
-
-        // The forward casts only matter nearer than move_dist + buffer: a
-        // farther hit leaves hit_pos at move_dist, takes no slide and the
-        // normal / high_hit it sets are read only by the slide (bound with a
-        // margin of kCastSlack so no value near a decision is ever cut).
-        const float fwd_b = (move_dist + buffer) + kCastSlack;
-        ray_o = x + v_norm * buffer * 0.5f;
-        ray_o.z += low_check;
-        // the low cast and (standing / crouching) the high cast from
-        // (ray_o.xy, x.z + top), traversed together
-        SphereHit hl, hh;
-        hh.t = kFltMax;
-        castNear2D(bvh, sc, ray_o, x.z + top, v_norm, fwd_b, pose != kProne, hl, hh);
-        float low_dist = hl.t;
-        if (hl.t < kFltMax) normal = hl.n;
-        float high_dist = low_dist;
-        bool high_hit = false;
-        if (pose != kProne) {
-            high_dist = hh.t;
-            if (high_dist < low_dist) {
-                low_dist = high_dist;
-                normal = hh.n;
-                high_hit = true;
-            }
-        }
-        bool stuck = low_dist == 0.0f || high_dist == 0.0f;
-        low_dist = fmaxD(0.0f, low_dist - buffer);
-        high_dist = fmaxD(0.0f, high_dist - buffer);
-        hit_pos = x + v_norm * fminD(low_dist, move_dist);
-
-        if (move_dist > low_dist) {
-            Vec3 slide_dir = normalize(cross(kUp, normal));
-            if (dot(slide_dir, v_norm) < 0) slide_dir = -slide_dir;
-            ray_o = x + v_norm * low_dist;
-            ray_o.z += high_hit ? top : low_check;
-            float max_move = move_dist - low_dist;
-            // only min(slide - buffer, max_move) is used
-            float slide = castNearD(bvh, sc, ray_o, slide_dir, (max_move + buffer) + kCastSlack).t;
-            slide = fmaxD(0.0f, slide - buffer);
-            slide = fminD(slide, max_move);
-            if (slide > 0.0f) hit_pos = hit_pos + slide_dir * slide;
-        }
-
-        ground_check = hit_pos;
-        ground_check.z += top;
-        // min(ground_dist, top) is used, and whether there is ground at all
-        ground_dist = castFirstNearD(bvh, sc, ground_check, -kUp, 2.f * top + 10.f);
-        if (ground_dist == kFltMax) break;
-        stuck_path = (ground_dist <= 0.0f || stuck);
-        cont = true;
-    } while (false);
-
-    float hd4[4] = { 0.f, 0.f, 0.f, 0.f };
-    stuckCastsD(bvh, stuck_path, x, v_norm, low_check, hd4);
-
-    while (cont) {
-        if (stuck_path) {
-            float furthest = 0.0f;
-            int best_dir = -1;
-            for (int dir = 0; dir < 4; dir++) {
-                if (hd4[dir] > furthest) {
-                    furthest = hd4[dir];
-                    best_dir = dir;
-                }
-            }
-            if (best_dir != -1) {
-                Vec3 dv = rotate2DD(v_norm, (float)best_dir * 3.14159f * 0.5f);
-                hit_pos = x + dv * (fminD(furthest - r * 2.0f, -buffer));
-                ground_check = hit_pos;
-                ground_check.z += top;
-                ground_dist = bvhSphereCastD(bvh, ground_check, -kUp, r).t;
-                if (ground_dist == kFltMax) break;
-            }
-        }
-
-        float fall_dist = fminD(ground_dist, top) + r;
-        Vec3 np = ground_check;
-        np.z -= fall_dist;
-        Vec3 to_new = np - x;
-        float to_new_dist = length(to_new);
-        if (to_new_dist == 0.f) break;
-        new_pos = np;
-        new_vel = to_new / c::kDeltaT;
-        break;
-    }
-    // updateMoveStateSystem (sim.cpp:1030-1039)
-    stPos(S, g, new_pos);
-    stVel(S, g, new_vel);
-}
-
-// sim.cpp:1041-1104 fallSystem + updateMoveStatePostFallSystem
-template <class LBVH>
-__device__ __forceinline__ void fallD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int64_t g)
-{
-    if (S.alive[g] == 0.f) return;
-    const float fall_rate = 386.08858267717f;
-    const float cast_offset = c::kAgentRadius;
-    Vec3 pos = ldPos(S, g);
-    Vec3 ray_o = pos;
-    ray_o.z += c::kAgentRadius + cast_offset;
-    // min(ground - cast_offset, fall_rate * dt) is used, and whether there
-    // is ground at all
-    float ground = castFirstNearD(bvh, sc, ray_o, -kUp, 2.f * (cast_offset + fall_rate * c::kDeltaT) + 10.f);
-    if (ground == kFltMax || ground < cast_offset) return;
-    float fall = fminD(ground - cast_offset, fall_rate * c::kDeltaT);
-    pos.z -= fall;
-    S.pz[g] = pos.z;
 }
 
 // sim.cpp:1443-1615 fireSystem
@@ -1793,8 +1130,6 @@ __device__ void subzoneSystemD(const DevState &S, const SceneDev &sc, int w)
     S.subState[w] = (int32_t)st;
 }
 
-__device__ __forceinline__ float4 *crumbPtr(const DevState &S, int w) { return &S.crumbs[(int64_t)w * kMaxCrumbs * 2]; }
-
 // sim.cpp:4845-4889 leaveBreadcrumbsSystem, agent part: refresh own last
 // crumb or request a new one (returns true; appended in agent order by the
 // world lane, the requests handed over in LDS).  The penalty's reset to 0
@@ -2350,8 +1685,6 @@ __device__ __forceinline__ void goalRegionsD(const DevState &S, const SceneDev &
 // cells outside the y<40, x<40 quadrant, i.e. already set (k_init_explore).
 // Bits live in 8 x 8-cell u64 tiles; the current tile is cached in SoA
 // columns and written back to the row when the agent leaves it.
-__device__ __forceinline__ int exploreBitD(int cx, int cy) { return (cy & 7) * 8 + (cx & 7); }
-__device__ __forceinline__ int exploreTileD(int cx, int cy) { return (cy >> 3) * kExploreTilesX + (cx >> 3); }
 
 __device__ void exploreVisitedD(const DevState &S, int w, int64_t g)
 {
@@ -2575,19 +1908,6 @@ __device__ __forceinline__ float zoneRewardD(const DevState &S, const SceneDev &
 }
 
 // ====================================================== kernels
-constexpr int kBlock = 256;
-
-// XCD-aware block order (cdna_hip_programming.md T1): the dispatcher deals
-// consecutive blocks round-robin to the 8 XCDs, each with its own L2; the
-// step kernels index worlds / agents by block, so neighbouring blocks share
-// cache lines of the per-world and per-agent columns.  Renumbered, each XCD
-// runs one contiguous range of blocks (bijective for any grid size).
-__device__ __forceinline__ uint32_t xcdBlockId()
-{
-    const uint32_t nwg = gridDim.x, orig = blockIdx.x;
-    const uint32_t xcd = orig % 8u, q = nwg / 8u, r = nwg % 8u;
-    return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + orig / 8u;
-}
 
 // Persistent-entity setup + the Sim constructor's initWorld(ctx, true)
 // (sim.cpp:5850-5980, level_gen.cpp:19-328).  One thread per world.
@@ -2667,48 +1987,6 @@ __global__ void __launch_bounds__(64) k_reset_only(DevState S, SceneDev sc)
 
 // The Step graph up to and including resetSystem, one workgroup per tile of
 // floor(256 / N) worlds, one lane per agent.
-// Step graph part 1 (sim.cpp:5299-5320 up to updateMoveStatePostFall): the
-// per-agent systems, which read no other agent's state.  Lane = agent, no
-// barriers, so sphere-cast latency overlaps across the whole grid.
-// apw: agents per wave (64, or fewer on small batches: a wave runs the
-// longest of its lanes' sphere-cast chains, so when the batch leaves SIMDs
-// idle, fewer agents per wave shorten every wave; launchMove picks it).
-template <class LBVH>
-__device__ __forceinline__ void moveBody(const DevState &S, const SceneDev &sc, int apw, char *img)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    LBVH bvh = stageBVHSphere<LBVH>(LBVH::kStaged ? smem : img, sc);
-    bvh.stats = S.stats;
-    [&]() {
-        const int lane = threadIdx.x & 63;
-        if (lane >= apw) return;
-        const int64_t wave = ((int64_t)xcdBlockId() * blockDim.x + threadIdx.x) >> 6;
-        const int64_t g = wave * apw + lane;
-        if (g >= S.A) return;
-        if (S.stats) statAdd(S.stats + kStatAliveAgents, S.alive[g] != 0.f ? 1u : 0u);
-        planAStarD(S, sc, g);
-        if (sc.replayOn) return; // pvpReplayLogic replaces the gameplay systems (sim.cpp:5587-5605)
-        applyBotActionsD(S, g);
-        pvpMovementD(S, g);
-        pvpAimD(S, g);
-        applyVelocityD(S, sc, bvh, g);
-        fallD(S, sc, bvh, g);
-    }();
-}
-
-// Each kernel that walks a BVH is its body instantiated over the LDS view and
-// (`_g`, with the images as one more argument) over the global one; the host
-// launcher picks by SceneImages::residency.
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) k_move(DevState S, SceneDev sc, int apw)
-{
-    moveBody<LBVHL>(S, sc, apw, nullptr);
-}
-
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) k_move_g(DevState S, SceneDev sc, int apw, SceneImages img)
-{
-    moveBody<LBVHG>(S, sc, apw, img.sphere);
-}
-
 // Step graph part 2 (fireSystem onward): per-world phases.  A workgroup
 // holds floor(kSimBlock / N) whole worlds, lane = agent, phases separated
 // by workgroup barriers.
@@ -3019,69 +2297,6 @@ __global__ void __launch_bounds__(kSimBlock) MP_SIM_ATTR __attribute__((flatten)
     simBody<LBVHG>(S, sc, img.sphere);
 }
 
-// utils.cpp:169-184 inFrustum
-__device__ __forceinline__ bool inFrustumD(const SceneDev &sc, Vec3 vp)
-{
-    bool in = true;
-    in = in && vp.y * sc.frustum[1] - fabs_(vp.x) * sc.frustum[0] > -c::kAgentRadius;
-    in = in && vp.y * sc.frustum[3] - fabs_(vp.z) * sc.frustum[2] > -c::kAgentRadius;
-    return in;
-}
-
-// opponentsWriteVisibilitySystem (sim.cpp:2526-2560) + isAgentVisible
-// (utils.cpp:169-271): agent i sees opponent k if any of 4 sample points on
-// k (bottom, top, left, right) passes the view tests and the closest hit of
-// the ray toward it is k's capsule.
-//
-// Ray compaction: lane = (agent, opponent); each 64-lane wave holds whole
-// agents (floor(64/T) of them).  Phase A tests the sample points (cheap) and
-// reserves LDS slots for the candidate rays; phase B traces the compacted
-// ray list with every lane of the workgroup, OR-ing hits into per-agent LDS
-// masks; phase C writes one mask byte per agent.  Only ~1.5 of the 4 points
-// survive the view tests on average, so the dense pass replaces a per-lane
-// loop that ran at roughly a third of the wave's lanes.
-constexpr int kVisMaxRays = kBlock * 4;
-
-// k_vis stages its block's agents with their worlds' whole rosters (the
-// opponents the block's lanes test and every capsule a ray may meet) in LDS
-// after the BVH image: 4 waves x floor(64/T) agents plus up to N-1 agents of
-// the partial first and last worlds.  Columns: px, py, pz, view height,
-// aim quaternion (w, x, y, z), alive.
-constexpr int kVisStageCols = 9;
-__host__ __device__ __forceinline__ int visStageAgents(int T, int N) { return (kBlock / 64) * (64 / T) + 2 * (N - 1); }
-
-__device__ __forceinline__ Vec3 visSamplePointD(const DevState &S, int64_t gt, Vec3 delta_right, int p)
-{
-    Vec3 pt = ldPos(S, gt);
-    pt.z += p == 0 ? c::kAgentRadius : viewHeightD(S.curPose[gt]);
-    if (p == 2) pt = pt - delta_right;
-    if (p == 3) pt = pt + delta_right;
-    return pt;
-}
-
-// utils.cpp:169-271 isAgentVisible for one (viewer, target) pair, lane-wise
-// (the flank reward's checks; k_vis batches the opponent checks instead).
-template <class LBVH>
-__device__ __forceinline__ bool isAgentVisibleD(const DevState &S, const SceneDev &sc, const LBVH &bvh, int w, Vec3 org,
-                                Quat aim_rot, int target)
-{
-    const int N = S.N;
-    const int64_t g0 = (int64_t)w * N;
-    const Quat inv_rot = qinv(aim_rot);
-    const Vec3 delta_right = rotateVec(aim_rot, kRight) * 0.9f * c::kAgentRadius;
-    for (int p = 0; p < 4; p++) {
-        Vec3 to_test = visSamplePointD(S, g0 + target, delta_right, p) - org;
-        Vec3 view = rotateVec(inv_rot, to_test);
-        if (view.y <= 0.f) continue;
-        if (!inFrustumD(sc, view)) continue;
-        const float len = length(to_test);
-        if (len < c::kAgentRadius) continue;
-        to_test = to_test / len;
-        if (visibleRayD(bvh, S.px, S.py, S.pz, g0, N, org, to_test, target)) return true;
-    }
-    return false;
-}
-
 // sim.cpp:4202-4278 flankRewardSystem (Task.Zone with train_flank): small
 // bonuses for teammates out of sight or >= 100 units away and for each
 // opponent that cannot see the agent (judged with the agent's own aim),
@@ -3128,1201 +2343,6 @@ __device__ __forceinline__ float flankRewardD(const DevState &S, const SceneDev 
     return r;
 }
 
-template <class LBVH>
-__device__ __forceinline__ void visBody(const DevState &S, const SceneDev &sc, char *img)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ uint16_t rays[kVisMaxRays];  // (lane << 2) | point
-    __shared__ uint16_t rays2[kVisMaxRays]; // phase B2: indices into rays
-    __shared__ uint32_t masks[kBlock]; // per agent of the block (<= 4 waves x 64/T)
-    __shared__ uint32_t nrays, nrays2;
-    if (threadIdx.x == 0) {
-        nrays = 0;
-        nrays2 = 0;
-    }
-    masks[threadIdx.x] = 0;
-    const int T = S.T, N = S.N;
-    const int apw = 64 / T;
-    const int wl = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)xcdBlockId() * blockDim.x + threadIdx.x) >> 6;
-    const int64_t agent0 = (((int64_t)xcdBlockId() * blockDim.x) >> 6) * apw; // first agent of the block
-    const int nsMax = visStageAgents(T, N);
-    float *st = (float *)(smem + (LBVH::kStaged ? (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16 : 0));
-    const int64_t s0 = (agent0 / N) * N;
-    {
-        const int64_t a_hi = min(S.A, agent0 + (int64_t)(kBlock / 64) * apw);
-        const int ns = agent0 < a_hi ? (int)(((a_hi - 1) / N + 1) * N - s0) : 0;
-        for (int k = threadIdx.x; k < ns; k += kBlock) {
-            const int64_t g = s0 + k;
-            st[0 * nsMax + k] = S.px[g];
-            st[1 * nsMax + k] = S.py[g];
-            st[2 * nsMax + k] = S.pz[g];
-            st[3 * nsMax + k] = viewHeightD(S.curPose[g]);
-            st[4 * nsMax + k] = S.aw[g];
-            st[5 * nsMax + k] = S.ax[g];
-            st[6 * nsMax + k] = S.ay[g];
-            st[7 * nsMax + k] = S.az[g];
-            st[8 * nsMax + k] = S.alive[g];
-        }
-    }
-    // The collision tree, as isAgentVisible walks it (the reference has one
-    // tree): which triangles a traversal reaches depends on the tree for rays
-    // along a zero-margin child box face, so another tree can answer
-    // differently (DESIGN.md section 2 definition 4).  Barrier.
-    const LBVH bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img, sc);
-    auto sPos = [&](int64_t g) {
-        const int l = (int)(g - s0);
-        return v3(st[0 * nsMax + l], st[1 * nsMax + l], st[2 * nsMax + l]);
-    };
-    auto sAim = [&](int64_t g) {
-        const int l = (int)(g - s0);
-        return quat(st[4 * nsMax + l], st[5 * nsMax + l], st[6 * nsMax + l], st[7 * nsMax + l]);
-    };
-    auto sView = [&](int64_t g) { return st[3 * nsMax + (int)(g - s0)]; };
-    auto sAlive = [&](int64_t g) { return st[8 * nsMax + (int)(g - s0)]; };
-    // visSamplePointD from the stage
-    auto sSample = [&](int64_t gt, Vec3 delta_right, int p) {
-        Vec3 pt = sPos(gt);
-        pt.z += p == 0 ? c::kAgentRadius : sView(gt);
-        if (p == 2) pt = pt - delta_right;
-        if (p == 3) pt = pt + delta_right;
-        return pt;
-    };
-
-    // ---- phase A: view tests, reserve ray slots
-    {
-        const int64_t g = wave * apw + wl / T;
-        const int k = wl % T;
-        const bool valid = wl < apw * T && g < S.A;
-        uint32_t cand = 0;
-        if (valid) {
-            const int w = (int)(g / N);
-            const int i = (int)(g - (int64_t)w * N);
-            const int64_t gt = (int64_t)w * N + ((i / T) ^ 1) * T + k;
-            if (sAlive(g) != 0.f && sAlive(gt) != 0.f) {
-                Vec3 org = sPos(g);
-                org.z += sView(g);
-                const Quat aim_rot = sAim(g);
-                const Quat inv_rot = qinv(aim_rot);
-                const Vec3 delta_right = rotateVec(aim_rot, kRight) * 0.9f * c::kAgentRadius;
-#pragma unroll
-                for (int p = 0; p < 4; p++) {
-                    Vec3 to_test = sSample(gt, delta_right, p) - org;
-                    Vec3 view = rotateVec(inv_rot, to_test);
-                    if (view.y <= 0.f) continue;
-                    if (!inFrustumD(sc, view)) continue;
-                    if (length(to_test) < c::kAgentRadius) continue;
-                    cand |= 1u << p;
-                }
-            }
-        }
-        const int nc = __popc(cand);
-        if (S.stats) {
-            uint32_t pair = 0;
-            if (valid && sAlive(g) != 0.f) {
-                const int64_t gt2 = (g / N) * N + (((int)(g % N) / T) ^ 1) * T + k;
-                pair = sAlive(gt2) != 0.f ? 1u : 0u;
-            }
-            statAdd(S.stats + kStatLosPairs, pair);
-            statAdd(S.stats + kStatLosRays, (uint32_t)nc);
-        }
-        // Ray-slot reservation: the wave's exclusive prefix sum of its
-        // lanes' candidate counts (4 ballots of one bit each, mbcnt), one
-        // LDS atomic per wave for the base.
-        uint32_t before = 0, wtotal = 0;
-#pragma unroll
-        for (int bit = 0; bit < 3; bit++) {
-            const uint64_t m = __ballot((nc >> bit) & 1);
-            before += (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << bit;
-            wtotal += (uint32_t)__popcll(m) << bit;
-        }
-        uint32_t base = 0;
-        if (wl == 0 && wtotal) base = atomicAdd(&nrays, wtotal);
-        base = __shfl(base, 0);
-        if (nc) {
-            uint32_t slot = base + before;
-            const uint16_t lane_id = (uint16_t)(threadIdx.x << 2);
-            for (int p = 0; p < 4; p++)
-                if (cand & (1u << p)) rays[slot++] = (uint16_t)(lane_id | p);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase B: the compacted rays.  B1 decides what needs no traversal
-    // (target capsule missed, occluder hint hit); the rest are compacted
-    // again so B2's traversals run in dense waves (a wave of mixed rays
-    // otherwise idles all but its few traversing lanes).
-    const uint32_t total = nrays;
-    const uint32_t numTris = (uint32_t)(sc.numVerts / 3);
-    // the occluder hint stores triangle ids as u16 with 0xffff = none: off
-    // for scenes of 65,535 triangles or more
-    const bool hints = numTris < 0xffffu;
-    auto rayOf = [&](uint32_t r, int64_t &g, int &k, int &p, int64_t &g0, int &target, Vec3 &org, Vec3 &dir) {
-        const uint32_t d = rays[r];
-        const int lane = (int)(d >> 2);
-        p = (int)(d & 3);
-        const int lwl = lane & 63;
-        g = ((((int64_t)xcdBlockId() * blockDim.x + lane) >> 6) * apw) + lwl / T;
-        k = lwl % T;
-        const int w = (int)(g / N);
-        const int i = (int)(g - (int64_t)w * N);
-        g0 = (int64_t)w * N;
-        target = ((i / T) ^ 1) * T + k;
-        org = sPos(g);
-        org.z += sView(g);
-        const Quat aim_rot = sAim(g);
-        const Vec3 delta_right = rotateVec(aim_rot, kRight) * 0.9f * c::kAgentRadius;
-        Vec3 to_test = sSample(g0 + target, delta_right, p) - org;
-        const float len = length(to_test);
-        dir = to_test / len;
-    };
-    for (uint32_t r = threadIdx.x; r < total; r += kBlock) {
-        int64_t g, g0;
-        int k, p, target;
-        Vec3 org, dir;
-        rayOf(r, g, k, p, g0, target, org, dir);
-        float t_c;
-        const int l0 = (int)(g0 - s0);
-        auto capsule = [&](int j) { return v3(st[0 * nsMax + l0 + j], st[1 * nsMax + l0 + j], st[2 * nsMax + l0 + j]); };
-        if (!visibleQuickD(bvh, capsule, org, dir, target,
-                           hints ? S.visOcc + (g * T + k) * 4 + p : nullptr, numTris, t_c))
-            rays2[atomicAdd(&nrays2, 1u)] = (uint16_t)r;
-    }
-    __syncthreads();
-    const uint32_t total2 = nrays2;
-    if (S.stats && threadIdx.x == 0) atomicAdd(S.stats + kStatLosTraced, (unsigned long long)total2);
-    for (uint32_t q = threadIdx.x; q < total2; q += kBlock) {
-        int64_t g, g0;
-        int k, p, target;
-        Vec3 org, dir;
-        rayOf(rays2[q], g, k, p, g0, target, org, dir);
-        // t_c again (the same bits as in B1)
-        const int l0 = (int)(g0 - s0);
-        auto capsule = [&](int j) { return v3(st[0 * nsMax + l0 + j], st[1 * nsMax + l0 + j], st[2 * nsMax + l0 + j]); };
-        Vec3 ct = capsule(target);
-        ct.z += kCapsuleRadius;
-        const float t_c = intersectRayZOriginCapsule(org - ct, dir, kCapsuleRadius, kCapsuleSegment);
-        const bool seen = visibleFullD(bvh, capsule, N, org, dir, target, t_c,
-                                       hints ? S.visOcc + (g * T + k) * 4 + p : nullptr);
-        if (seen) atomicOr(&masks[(int)(g - agent0)], 1u << k);
-        if (S.stats) statAdd(S.stats + kStatLosSeen, seen ? 1u : 0u);
-    }
-    __syncthreads();
-
-    // ---- phase C: one byte per agent
-    {
-        const int64_t g = wave * apw + wl / T;
-        const bool valid = wl < apw * T && g < S.A;
-        if (valid && wl % T == 0) S.visMask[g] = (uint8_t)masks[(int)(g - agent0)];
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) k_vis(DevState S, SceneDev sc)
-{
-    visBody<LBVHL>(S, sc, nullptr);
-}
-
-__global__ void __launch_bounds__(kBlock) k_vis_g(DevState S, SceneDev sc, SceneImages img)
-{
-    visBody<LBVHG>(S, sc, img.sphere);
-}
-
-__device__ __forceinline__ Vec3 normalizedPosD(const SceneDev &sc, Vec3 p) // sim.cpp:2693-2718
-{
-    float min_x = sc.worldBounds.pMin.x, min_y = sc.worldBounds.pMin.y, min_z = sc.worldBounds.pMin.z;
-    float max_x = sc.worldBounds.pMax.x, max_y = sc.worldBounds.pMax.y, max_z = sc.worldBounds.pMax.z;
-    float xr = max_x - min_x, yr = max_y - min_y, zr = max_z - min_z;
-    float x = (p.x - min_x) / xr, y = (p.y - min_y) / yr, z = (p.z - min_z) / zr;
-    return v3(clampf(x, 0.f, 1.f), clampf(y, 0.f, 1.f), clampf(z, 0.f, 1.f));
-}
-
-struct SelfFrame {
-    Vec3 pos;
-    Quat invRot;
-    float yaw, pitch;
-};
-
-__device__ __forceinline__ void relAnglesD(const SelfFrame &sf, Vec3 to, float &dist_out, float &yaw_out,
-                                           float &pitch_out)
-{
-    float d = length(to);
-    if (d < 1e-2f) {
-        dist_out = 0.f; yaw_out = 0.f; pitch_out = 0.f;
-        return;
-    }
-    to = to / d;
-    float new_yaw = -atan2f_(to.x, to.y);
-    float new_pitch = asinf_(clampf(to.z, -1.f, 1.f));
-    float yaw_delta = new_yaw - sf.yaw;
-    float pitch_delta = new_pitch - sf.pitch;
-    if (yaw_delta > kPi) yaw_delta -= 2.f * kPi;
-    else if (yaw_delta < -kPi) yaw_delta += 2.f * kPi;
-    dist_out = d; yaw_out = yaw_delta; pitch_out = pitch_delta;
-}
-
-__device__ __forceinline__ Vec3 normalizedPosUnclampedD(const SceneDev &sc, Vec3 p)
-{
-    float min_x = sc.worldBounds.pMin.x, min_y = sc.worldBounds.pMin.y, min_z = sc.worldBounds.pMin.z;
-    float max_x = sc.worldBounds.pMax.x, max_y = sc.worldBounds.pMax.y, max_z = sc.worldBounds.pMax.z;
-    float xr = max_x - min_x, yr = max_y - min_y, zr = max_z - min_z;
-    return v3((p.x - min_x) / xr, (p.y - min_y) / yr, (p.z - min_z) / zr);
-}
-
-// ---- k_obs: pvpOpponentMasksSystem (sim.cpp:2562-2614), pvpObservationsSystem
-// (sim.cpp:2645-3052) and fullTeamObservationsSystem (sim.cpp:3054-3301).
-//
-// Load first, then store.  gfx9's vector-memory counter retires loads and
-// stores in issue order, so a load issued after a burst of stores cannot be
-// waited for without waiting for those stores' write acknowledgements too.
-// The round-1..4 k_obs gathered each world-mate's fields from HBM/L2 inside
-// its slot loop, between the previous slot's row stores: every slot paid a
-// full store round trip (55 `s_waitcnt vmcnt(0)` in its ISA; ~95 us per wave
-// for ~141 KB of rows, 3.4 TB/s).  Now every input is read before the first
-// store: a block (256 consecutive agents) stages the columns of every agent
-// of its worlds in LDS (<= 256 + 2 (N - 1) agents, coalesced column loads),
-// each lane loads its own rotation and world fields, and from then on the
-// kernel only reads LDS and stores.
-//
-// Rows leave through a per-wave LDS transpose, half a wave (32 rows) at a
-// time so the stage fits next to the agent columns (3 blocks per CU): a
-// lane computes its row in registers, its half writes the rows to LDS, and
-// every lane of the wave stores whole row pieces (float4 where the rows are
-// 16-B aligned), so a store instruction writes a few whole 128-B lines
-// instead of one 4-16 B piece of 64 different rows.
-constexpr int kObsBlock = 256;
-constexpr int kObsStageMax = kObsBlock + 2 * (kMaxAgents - 1); // the block's agents plus a partial world at each end
-enum : int {
-    kOsPX, kOsPY, kOsPZ, kOsVX, kOsVY, kOsVZ, kOsYaw, kOsPitch, kOsDYV, kOsDPV, kOsHP, kOsFired, kOsAlive, // f32
-    kOsCurPose, kOsTgtPose, kOsWeapon, kOsVis, kOsTrans, kOsFlags, kOsShot, kOsHeal, kOsMag0, kOsMag1,      // i32
-    kObsCols
-};
-constexpr int kObsRowPad = kOtherObs + 4; // LDS row stride (floats) of the 32-float rows: 16-B aligned
-constexpr int kObsSpanPad = 44;           // floats per staged row: >= kObsRowPad and the 43-float self obs
-
-// The block's agent columns in LDS (index = global agent id - s0).
-struct ObsStage {
-    const float (*c)[kObsStageMax];
-    __device__ __forceinline__ float f(int col, int k) const { return c[col][k]; }
-    __device__ __forceinline__ int32_t i(int col, int k) const { return __float_as_int(c[col][k]); }
-    __device__ __forceinline__ Vec3 pos(int k) const { return v3(c[kOsPX][k], c[kOsPY][k], c[kOsPZ][k]); }
-    __device__ __forceinline__ Vec3 vel(int k) const { return v3(c[kOsVX][k], c[kOsVY][k], c[kOsVZ][k]); }
-    __device__ __forceinline__ bool alive(int k) const { return c[kOsAlive][k] != 0.f; }
-};
-
-// fillCommonOb (sim.cpp:2720-2774) of stage agent j into a register array;
-// returns alive.
-__device__ __forceinline__ bool fillCommonS(const ObsStage &st, const SceneDev &sc, const SelfFrame &sf, int j,
-                                            float *ob, float *pos_ob)
-{
-    ob[0] = 1.f;
-    if (!st.alive(j)) return false;
-    ob[1] = 1.f;
-    Vec3 np = normalizedPosD(sc, st.pos(j));
-    ob[2] = np.x; ob[3] = np.y; ob[4] = np.z;
-    pos_ob[0] = np.x; pos_ob[1] = np.y; pos_ob[2] = np.z;
-    ob[5] = 0.5f * ((st.f(kOsYaw, j) / kPi) + 1.f);
-    ob[6] = 0.5f * (st.f(kOsPitch, j) / (0.25f * kPi) + 1.f);
-    Vec3 rv = rotateVec(sf.invRot, st.vel(j));
-    ob[7] = rv.x; ob[8] = rv.y; ob[9] = rv.z;
-    ob[10] = st.f(kOsDYV, j); ob[11] = st.f(kOsDPV, j);
-    const int cp = st.i(kOsCurPose, j), tp = st.i(kOsTgtPose, j);
-    ob[12] = cp == kStand ? 1.f : 0.f;
-    ob[13] = cp == kCrouch ? 1.f : 0.f;
-    ob[14] = cp == kProne ? 1.f : 0.f;
-    ob[15] = tp == kStand ? 1.f : 0.f;
-    ob[16] = tp == kCrouch ? 1.f : 0.f;
-    ob[17] = tp == kProne ? 1.f : 0.f;
-    ob[18] = (float)st.i(kOsTrans, j) / (float)c::kPoseTransitionSpeed;
-    ob[19] = (st.i(kOsFlags, j) & kFlagInZone) ? 1.f : 0.f;
-    const int wt = st.i(kOsWeapon, j);
-    ob[20] = wt == 0 ? 1.f : 0.f;
-    ob[21] = wt == 1 ? 1.f : 0.f;
-    ob[22] = wt == 2 ? 1.f : 0.f;
-    return true;
-}
-
-__device__ __forceinline__ void fillCombatS(const ObsStage &st, int j, float *ob)
-{
-    ob[0] = st.f(kOsHP, j) / 100.f;
-    ob[1] = (float)st.i(kOsMag0, j);
-    ob[2] = (float)st.i(kOsMag1, j);
-    ob[3] = float(st.i(kOsHeal, j)) / float(c::kOutOfCombatSteps);
-}
-
-__device__ __forceinline__ void fillOtherS(const ObsStage &st, const SelfFrame &sf, int j, float *ob)
-{
-    relAnglesD(sf, st.pos(j) - sf.pos, ob[23], ob[24], ob[25]);
-    float rfy = st.f(kOsYaw, j) - sf.yaw;
-    float rfp = st.f(kOsPitch, j) - sf.pitch;
-    if (rfy > kPi) rfy -= 2.f * kPi;
-    else if (rfy < -kPi) rfy += 2.f * kPi;
-    ob[26] = rfy;
-    ob[27] = rfp;
-}
-
-// Half-wave row stage.  `buf` holds 32 rows (stride P <= kObsSpanPad floats)
-// and `offs` 32 row offsets.  Half h = lanes [32h, 32h + 32) of the wave's
-// m live lanes (a tail wave's lanes past A have returned).  Pattern:
-//   stage(h, ...) by the half's lanes -> waveSync -> flush*(h, ...) by every
-//   live lane -> waveSync (reads done before the next rows land).
-// The cross-lane exchange stays inside one wave: the wave's DS instructions
-// execute in issue order, so only the compiler needs ordering, which the
-// wavefront-scope fences of waveSync give.
-struct HalfStage {
-    float *buf;
-    int64_t *offs;
-    int lane, m;
-
-    __device__ __forceinline__ int halves() const { return m > 32 ? 2 : 1; }
-    __device__ __forceinline__ int rowsOf(int h) const { return m - 32 * h < 32 ? m - 32 * h : 32; }
-    __device__ __forceinline__ bool mine(int h) const { return (lane >> 5) == h; }
-    template <int P> __device__ __forceinline__ void stage(int h, const float *v, int n, int at = 0) const
-    {
-        if (mine(h))
-            for (int k = 0; k < n; k++) buf[(lane & 31) * P + at + k] = v[k];
-    }
-    __device__ __forceinline__ void stageOff(int h, int64_t off) const
-    {
-        if (mine(h)) offs[lane & 31] = off;
-    }
-    // Rows of half h back to back from dst (row r at dst + r * n; the
-    // caller passes dst at the half's first row).  float4 when dst is 16-B
-    // aligned (a world group starting off a 4-agent boundary is not).
-    template <int n, int P> __device__ __forceinline__ void flushSpan(int h, float *dst) const
-    {
-        const int total = rowsOf(h) * n;
-        auto val = [&](int f) {
-            const int r = f / n;
-            return buf[r * P + (f - r * n)];
-        };
-        if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-            const int q4 = total >> 2;
-            // rolled, one division per float4 (the four floats walk the
-            // staged row and wrap to the next): unrolled, the compiler hoisted
-            // per-element LDS offsets out of the loop and held ~40 VGPRs
-#pragma unroll 1
-            for (int j = lane; j < q4; j += m) {
-                int r = (4 * j) / n, c = 4 * j - r * n;
-                float v[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    v[q] = buf[r * P + c];
-                    if (++c == n) {
-                        c = 0;
-                        r++;
-                    }
-                }
-                reinterpret_cast<float4 *>(dst)[j] = make_float4(v[0], v[1], v[2], v[3]);
-            }
-            if (lane < (total & 3)) dst[4 * q4 + lane] = val(4 * q4 + lane);
-        } else {
-#pragma unroll 1
-            for (int f = lane; f < total; f += m) dst[f] = val(f);
-        }
-    }
-    // 32-float rows: row r of half h to arr[((gw0 + 32h + r) * slots + k) * 32]
-    // as 8 float4 pieces (each store instruction writes 8 whole rows).
-    template <int P> __device__ __forceinline__ void flushRows32(int h, float *arr, int slots, int k, int64_t gw0) const
-    {
-        static_assert(P % 4 == 0, "float4 rows");
-        const int nc = rowsOf(h) * (kOtherObs / 4);
-        float *base = arr + ((gw0 + 32 * h) * slots + k) * kOtherObs;
-        // <= 32 rows x 8 pieces over m >= rows lanes: at most 8 rounds (4 in a full wave)
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int c = lane + j * m;
-            if (c < nc) {
-                const int r = c >> 3, col = c & 7;
-                const uint32_t o = (uint32_t)(r * slots * kOtherObs + col * 4); // < 32 rows x 6 slots x 32
-                *reinterpret_cast<float4 *>(base + o) = reinterpret_cast<const float4 *>(buf + r * P)[col];
-            }
-        }
-    }
-    // Rows of n floats at per-row offsets (offs, staged with stageOff) into
-    // dst; wbits / zbits: wave ballots of "row exists" / "row is zeros".
-    template <int n, int P> __device__ __forceinline__ void flushOff(int h, float *dst, uint64_t wbits, uint64_t zbits) const
-    {
-        const uint32_t wb = (uint32_t)(wbits >> (32 * h)), zb = (uint32_t)(zbits >> (32 * h));
-        const int total = rowsOf(h) * n;
-#pragma unroll 1
-        for (int c = lane; c < total; c += m) {
-            const int r = c / n, col = c - r * n;
-            if ((wb >> r) & 1u) dst[offs[r] + col] = ((zb >> r) & 1u) ? 0.f : buf[r * P + col];
-        }
-    }
-    // The same for rows of n4 float4 (16-B aligned rows, P a multiple of 4).
-    template <int n4, int P> __device__ __forceinline__ void flushOff4(int h, float *dst, uint64_t wbits, uint64_t zbits) const
-    {
-        static_assert(P % 4 == 0, "float4 rows");
-        const uint32_t wb = (uint32_t)(wbits >> (32 * h)), zb = (uint32_t)(zbits >> (32 * h));
-        const int total = rowsOf(h) * n4;
-        for (int c = lane; c < total; c += m) {
-            const int r = c / n4, col = c - r * n4;
-            if ((wb >> r) & 1u)
-                reinterpret_cast<float4 *>(dst + offs[r])[col] =
-                    ((zb >> r) & 1u) ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4 *>(buf + r * P)[col];
-        }
-    }
-    // A contiguous span export (lane r's n floats at dst + r * n).
-    template <int n> __device__ __forceinline__ void putSpan(float *dst, const float *vals) const
-    {
-        constexpr int P = n | 1; // odd stride: conflict-free staging
-        static_assert(P <= kObsSpanPad, "span larger than the row stage");
-        for (int h = 0; h < halves(); h++) {
-            stage<P>(h, vals, n);
-            waveSync();
-            flushSpan<n, P>(h, dst + (int64_t)32 * h * n);
-            waveSync();
-        }
-    }
-};
-
-// kWire: the learner's rebuild of a shadow's rows from a wire message
-// (wire.hip launchWireUnpack): S is a view whose input columns point into
-// the message (the same SoA columns the sender's engine holds), the packed
-// pose / weapon / flags word is split here, the full-team rows (not
-// trainInterface outputs) are skipped, and a world whose episode counter
-// moved since the previous message has every last-known row written -- the
-// reset's clear on the sender (resetAgentD / resetPersistentEntitiesD),
-// then this step's updates -- exactly the rows the sender's k_obs leaves.
-// (One templated kernel, k_obs<false> on the step path and k_obs<true> =
-// "k_obs_wire" on the learner: the same body as a __device__ function under
-// two kernels compiled ~45% more instructions and ran 6% slower.)
-template <bool kWire>
-__global__ void __launch_bounds__(kObsBlock) __attribute__((amdgpu_waves_per_eu(3)))
-k_obs(DevState S, SceneDev sc, WireObs wo)
-{
-    __shared__ float ost[kObsCols][kObsStageMax];
-    __shared__ __attribute__((aligned(16))) float rowBuf[kObsBlock / 64][32 * kObsSpanPad];
-    __shared__ int64_t offBuf[kObsBlock / 64][32];
-    // a learner shadow out of wire sync keeps its rows (wire.hip wireOk);
-    // the same word for every thread of the grid
-    if (S.obsGate && (*S.obsGate & MPENV_WIRE_ERR_DESYNC)) return;
-    const int T = S.T, N = S.N;
-    const int64_t b0 = (int64_t)xcdBlockId() * kObsBlock; // < A (grid = ceil(A / kObsBlock))
-    const int64_t g = b0 + threadIdx.x;
-    const bool live = g < S.A;
-
-    // ---- loads: the block's worlds' agent columns, then this lane's own
-    // rotation and world fields (no store is issued before all of them)
-    const int64_t a_end = b0 + kObsBlock < S.A ? b0 + kObsBlock : S.A;
-    const int64_t s0 = (b0 / N) * N;
-    const int ns = (int)(((a_end - 1) / N + 1) * N - s0);
-    for (int k = threadIdx.x; k < ns; k += kObsBlock) {
-        const int64_t j = s0 + k;
-        ost[kOsPX][k] = S.px[j];
-        ost[kOsPY][k] = S.py[j];
-        ost[kOsPZ][k] = S.pz[j];
-        ost[kOsVX][k] = S.vx[j];
-        ost[kOsVY][k] = S.vy[j];
-        ost[kOsVZ][k] = S.vz[j];
-        ost[kOsYaw][k] = S.ayaw[j];
-        ost[kOsPitch][k] = S.apitch[j];
-        ost[kOsDYV][k] = S.dyv[j];
-        ost[kOsDPV][k] = S.dpv[j];
-        ost[kOsHP][k] = S.hp[j];
-        ost[kOsFired][k] = S.firedT[j];
-        ost[kOsAlive][k] = S.alive[j];
-        if constexpr (kWire) {
-            const uint32_t p = wo.packed[j]; // curPose | tgtPose << 8 | weapon << 16 | flags << 24
-            ost[kOsCurPose][k] = __int_as_float((int32_t)(p & 0xffu));
-            ost[kOsTgtPose][k] = __int_as_float((int32_t)((p >> 8) & 0xffu));
-            ost[kOsWeapon][k] = __int_as_float((int32_t)((p >> 16) & 0xffu));
-            ost[kOsVis][k] = __int_as_float((int32_t)S.visMask[j]);
-            ost[kOsTrans][k] = __int_as_float(S.transRem[j]);
-            ost[kOsFlags][k] = __int_as_float((int32_t)(p >> 24));
-        } else {
-            ost[kOsCurPose][k] = __int_as_float(S.curPose[j]);
-            ost[kOsTgtPose][k] = __int_as_float(S.tgtPose[j]);
-            ost[kOsWeapon][k] = __int_as_float(S.weapon[j]);
-            ost[kOsVis][k] = __int_as_float((int32_t)S.visMask[j]);
-            ost[kOsTrans][k] = __int_as_float(S.transRem[j]);
-            ost[kOsFlags][k] = __int_as_float(S.flags[j]);
-        }
-        ost[kOsShot][k] = __int_as_float(S.wasShot[j]);
-        ost[kOsHeal][k] = __int_as_float(S.autohealSteps[j]);
-        ost[kOsMag0][k] = __int_as_float(S.magazine[2 * j]);
-        ost[kOsMag1][k] = __int_as_float(S.magazine[2 * j + 1]);
-    }
-    const int64_t gs = live ? g : S.A - 1; // tail lanes load a valid agent's fields, then leave
-    const int w = (int)(gs / N);
-    const int i = (int)(gs - (int64_t)w * N);
-    const int team = i / T, off = i - team * T;
-    const Quat rot = ldRot(S, gs);
-    const int cur_step = S.curStep[w];
-    const int fm = team == 0 ? S.filtMatched0[w] : S.filtMatched1[w];
-    const int cz = S.curZone[w];
-    const int ctrl = S.controlling[w];
-    const int contested = S.contested[w], captured = S.captured[w];
-    const int until_point = S.stepsUntilPoint[w], zone_steps = S.zoneSteps[w];
-    const AABB za = sc.tab->zoneAABB[cz];
-    // the pure outputs' destinations: the engine's exports, or during a
-    // gpuStreamStep the caller's buffers (OutTab; uniform loads, issued with
-    // the other loads before the barrier)
-    float *oMasks = S.masks, *oFilters = S.filters, *oSelf = S.selfObs, *oSelfPos = S.selfPos;
-    float *oTm = S.tmObs, *oTmPos = S.tmPos, *oOpp = S.oppObs, *oOppPos = S.oppPos;
-    if (!kWire && S.outTab && S.outTab->on) {
-        const OutTab *t = S.outTab;
-        const int64_t b = S.outBase;
-        oMasks = t->masks + b * 6;
-        oFilters = t->filters + b;
-        oSelf = t->selfObs + b * kSelfObs;
-        oSelfPos = t->selfPos + b * 3;
-        oTm = t->tmObs + b * 5 * kOtherObs;
-        oTmPos = t->tmPos + b * 15;
-        oOpp = t->oppObs + b * 6 * kOtherObs;
-        oOppPos = t->oppPos + b * 18;
-    }
-    bool wreset = false; // kWire: the world's episode counter moved since the previous message
-    if constexpr (kWire) wreset = !wo.keyframe && wo.epPrev[w] != S.episodeCounter[w];
-    __syncthreads();
-    if (!live) return; // the flushes count the live lanes
-
-    const ObsStage st { ost };
-    const int lane = threadIdx.x & 63;
-    const int64_t gw0 = g - lane; // first agent of the wave
-    HalfStage hs;
-    hs.buf = rowBuf[threadIdx.x >> 6];
-    hs.offs = offBuf[threadIdx.x >> 6];
-    hs.lane = lane;
-    hs.m = (int)(S.A - gw0 < 64 ? S.A - gw0 : 64);
-    const int64_t g0 = (int64_t)w * N;
-    const int me = (int)(g - s0), l0 = (int)(g0 - s0); // stage indices: this agent, its world's first
-    const bool self_alive = st.alive(me);
-
-    // ---- masks
-    float mask[kMaxTeamSize];
-    for (int k = 0; k < kMaxTeamSize; k++) {
-        mask[k] = 0.f;
-        if (!self_alive || k >= T) continue;
-        const int jo = l0 + (team ^ 1) * T + k;
-        if (!st.alive(jo)) continue;
-        bool can_see = (st.i(kOsVis, me) >> k) & 1;
-        for (int t = 0; t < T - 1 && !can_see; t++) {
-            const int jt = l0 + team * T + (t < off ? t : t + 1);
-            if ((st.i(kOsVis, jt) >> k) & 1) can_see = true;
-        }
-        if (can_see) mask[k] = 1.f;
-        if (st.f(kOsFired, jo) >= 0) mask[k] = 1.f;
-    }
-    hs.putSpan<6>(oMasks + gw0 * 6, mask);
-    // teamKnowsLocation (mask[k] == 1) as bits for the opponent loop.
-    // Reading the float array there instead gave wrong last-known updates in
-    // round 2 -- a register miscompile of the float form ("k_obs
-    // mask read"); the bits form is taken right here.
-    uint32_t knowsBits = 0;
-    for (int k = 0; k < kMaxTeamSize; k++) knowsBits |= (mask[k] == 1.f ? 1u : 0u) << k;
-
-    oFilters[g] = (cur_step - fm < 5) ? 1.f : 0.f;
-
-    // ---- fullTeamObservationsSystem, per (world, team): the global
-    // observation and the zeroed slots past team_size (slot-0 agents)
-    const int64_t mine = (int64_t)w * 2 + team, theirs = (int64_t)w * 2 + (team ^ 1);
-    if (!kWire && off == 0) {
-        for (int s = T; s < kMaxTeamSize; s++) {
-            for (int k = 0; k < MPENV_FT_PLAYER_DIM; k++) S.ftPlayers[(mine * 6 + s) * MPENV_FT_PLAYER_DIM + k] = 0.f;
-            for (int k = 0; k < MPENV_FT_ENEMY_DIM; k++) S.ftEnemies[(mine * 6 + s) * MPENV_FT_ENEMY_DIM + k] = 0.f;
-            for (int k = 0; k < MPENV_FT_COMMON_DIM; k++) S.ftLastKnown[(mine * 6 + s) * MPENV_FT_COMMON_DIM + k] = 0.f;
-        }
-        float gob[MPENV_FT_GLOBAL_DIM];
-        gob[0] = team == 0 ? 0.f : 1.f;
-        gob[1] = team == 0 ? 1.f : 0.f;
-        gob[2] = float(c::kEpisodeLen - cur_step) / c::kEpisodeLen;
-        const Vec3 nc = normalizedPosUnclampedD(sc, (za.pMax + za.pMin) / 2.f);
-        gob[3] = nc.x; gob[4] = nc.y; gob[5] = nc.z;
-        gob[6] = ctrl == team ? 1.f : 0.f;
-        gob[7] = (ctrl != -1 && ctrl != team) ? 1.f : 0.f;
-        gob[8] = contested ? 1.f : 0.f;
-        gob[9] = captured ? 1.f : 0.f;
-        gob[10] = float(until_point) / float(c::kZonePointInterval);
-        gob[11] = float(zone_steps) / float(c::kNumStepsPerZone);
-        for (int k = 0; k < 4; k++) gob[12 + k] = cz == k ? 1.f : 0.f;
-        static_assert(MPENV_FT_GLOBAL_DIM == 16, "ft global row: 4 float4");
-        float4 *gdst = reinterpret_cast<float4 *>(&S.ftGlobal[mine * MPENV_FT_GLOBAL_DIM]);
-        for (int q = 0; q < 4; q++) gdst[q] = make_float4(gob[4 * q], gob[4 * q + 1], gob[4 * q + 2], gob[4 * q + 3]);
-    }
-
-    // ---- self observation
-    SelfFrame sf;
-    sf.pos = st.pos(me);
-    sf.invRot = qinv(rot);
-    sf.yaw = st.f(kOsYaw, me);
-    sf.pitch = st.f(kOsPitch, me);
-    {
-        float ob[kSelfObs];
-        float pos3[3];
-        for (int k = 0; k < kSelfObs; k++) ob[k] = 0.f;
-        pos3[0] = pos3[1] = pos3[2] = -1000.f;
-        if (fillCommonS(st, sc, sf, me, ob, pos3)) {
-            fillCombatS(st, me, &ob[23]);
-            float *zo = &ob[27];
-            Vec3 center = (za.pMax + za.pMin) / 2.f;
-            Vec3 nc = normalizedPosD(sc, center);
-            zo[0] = nc.x; zo[1] = nc.y; zo[2] = nc.z;
-            relAnglesD(sf, center - sf.pos, zo[3], zo[4], zo[5]);
-            zo[6] = (ctrl == team) ? 1.f : 0.f;
-            zo[7] = (ctrl != -1 && ctrl != team) ? 1.f : 0.f;
-            zo[8] = contested ? 1.f : 0.f;
-            zo[9] = captured ? 1.f : 0.f;
-            zo[10] = float(until_point) / float(c::kZonePointInterval);
-            zo[11] = float(zone_steps) / float(c::kNumStepsPerZone);
-            zo[12] = cz == 0 ? 1.f : 0.f;
-            zo[13] = cz == 1 ? 1.f : 0.f;
-            zo[14] = cz == 2 ? 1.f : 0.f;
-            zo[15] = cz == 3 ? 1.f : 0.f;
-        }
-        static_assert(kSelfObs == 43 && (kSelfObs | 1) <= kObsSpanPad, "self obs span");
-        hs.putSpan<kSelfObs>(oSelf + gw0 * kSelfObs, ob);
-        hs.putSpan<3>(oSelfPos + gw0 * 3, pos3);
-    }
-    const bool alive_ok = self_alive; // fillCommonOb's alive test of the agent itself
-
-    // Slot positions (teammate, opponent, last-known rows) are recomputed
-    // after each slot loop in fully unrolled form: written from inside the
-    // rolled loops, the arrays were indexed dynamically and went to scratch,
-    // whose loads would wait behind the row stores.
-    auto slotPos = [&](bool exists, int j, float *p3) {
-        if (exists && st.alive(j)) {
-            const Vec3 np = normalizedPosD(sc, st.pos(j));
-            p3[0] = np.x; p3[1] = np.y; p3[2] = np.z;
-        } else {
-            p3[0] = p3[1] = p3[2] = -1000.f;
-        }
-    };
-    auto mateIdx = [&](int k) { return l0 + team * T + (k < off ? k : k + 1); };
-    auto oppIdx = [&](int k) { return l0 + (team ^ 1) * T + k; };
-
-    // ---- teammates
-    {
-        for (int k = 0; k < kMaxTeamSize - 1; k++) {
-            float row[kOtherObs];
-            float unused[3];
-            for (int q = 0; q < kOtherObs; q++) row[q] = 0.f;
-            if (alive_ok && k < T - 1) {
-                const int jt = mateIdx(k);
-                if (fillCommonS(st, sc, sf, jt, row, unused)) {
-                    fillOtherS(st, sf, jt, row);
-                    fillCombatS(st, jt, &row[28]);
-                }
-            }
-            for (int h = 0; h < hs.halves(); h++) {
-                hs.stage<kObsRowPad>(h, row, kOtherObs);
-                waveSync();
-                hs.flushRows32<kObsRowPad>(h, oTm, 5, k, gw0);
-                waveSync();
-            }
-        }
-        float tpos[15];
-#pragma unroll
-        for (int k = 0; k < kMaxTeamSize - 1; k++) slotPos(alive_ok && k < T - 1, mateIdx(k), &tpos[3 * k]);
-        hs.putSpan<15>(oTmPos + gw0 * 15, tpos);
-    }
-
-    // ---- opponents (+ last known)
-    {
-        uint32_t lkWrite = 0, lkKeep = 0; // per slot: last-known row written / kept (else cleared)
-        for (int k = 0; k < kMaxTeamSize; k++) {
-            float row[kOtherObs];
-            float unused[3];
-            for (int q = 0; q < kOtherObs; q++) row[q] = 0.f;
-            // last-known slot: cleared (opponent dead / just killed), then
-            // overwritten with the observation when the team knows the location
-            bool lk_write = false, lk_keep = false;
-            if (alive_ok && k < T) {
-                const int jo = oppIdx(k);
-                if (!fillCommonS(st, sc, sf, jo, row, unused)) {
-                    lk_write = true;
-                } else {
-                    fillOtherS(st, sf, jo, row);
-                    if (st.i(kOsFlags, jo) & kFlagWasKilled) lk_write = true;
-                    row[28] = (float)st.i(kOsShot, jo);
-                    row[29] = st.f(kOsFired, jo) >= 0.f ? 1.f : 0.f;
-                    row[30] = ((st.i(kOsVis, me) >> k) & 1) ? 1.f : 0.f;
-                    // teamKnowsLocation (sim.cpp:2995-3003)
-                    const bool knows = (knowsBits >> k) & 1u;
-                    row[31] = knows ? 1.f : 0.f;
-                    lk_keep = knows;
-                    lk_write = lk_write || knows;
-                }
-            }
-            lk_write = lk_write || wreset;
-            lkWrite |= (lk_write ? 1u : 0u) << k;
-            lkKeep |= (lk_keep ? 1u : 0u) << k;
-            if (S.stats) statAdd(S.stats + kStatLkRows, lk_write ? 1u : 0u);
-            const uint64_t wb = __ballot(lk_write), zb = __ballot(!lk_keep);
-            for (int h = 0; h < hs.halves(); h++) {
-                hs.stage<kObsRowPad>(h, row, kOtherObs);
-                hs.stageOff(h, (g * 6 + k) * kOtherObs);
-                waveSync();
-                hs.flushRows32<kObsRowPad>(h, oOpp, 6, k, gw0);
-                // the staged row is also the last-known copy
-                hs.flushOff4<kOtherObs / 4, kObsRowPad>(h, S.lkObs, wb, zb);
-                waveSync();
-            }
-        }
-        float opos[18];
-#pragma unroll
-        for (int k = 0; k < kMaxTeamSize; k++) slotPos(alive_ok && k < T, oppIdx(k), &opos[3 * k]);
-        hs.putSpan<18>(oOppPos + gw0 * 18, opos);
-        // last-known positions: the written slots of each row (kept: the
-        // observed position, cleared: -1000)
-        {
-            float lpos[18];
-#pragma unroll
-            for (int q = 0; q < 18; q++) lpos[q] = ((lkKeep >> (q / 3)) & 1u) ? opos[q] : -1000.f;
-            constexpr int P = 19;
-            for (int h = 0; h < hs.halves(); h++) {
-                hs.stage<P>(h, lpos, 18);
-                hs.stageOff(h, (int64_t)lkWrite); // the row's slot mask (rows at g * 18)
-                waveSync();
-                const int total = hs.rowsOf(h) * 18;
-                float *dst = S.lkPos + (gw0 + 32 * h) * 18;
-#pragma unroll 1
-                for (int c = lane; c < total; c += hs.m) {
-                    const int r = c / 18, col = c - r * 18;
-                    if ((hs.offs[r] >> (col / 3)) & 1) dst[c] = hs.buf[r * P + col];
-                }
-                waveSync();
-            }
-        }
-    }
-
-    // ---- fullTeamObservationsSystem, the part owned by agent g (team, slot
-    // off): its player slot in its own team's interface, its enemy and
-    // last-known slots in the other team's interface (the common block is the
-    // same in all three, the one-hot id is the slot).  Positions are
-    // normalised without the clamp pvpObservations applies.  The lidar copy is
-    // fused into k_lidar.
-    if constexpr (!kWire) {
-        const bool alive = self_alive;
-        // enemy-only fields first: they decide whether the last-known slot
-        // receives the common block
-        const float fired = alive && st.f(kOsFired, me) >= 0.f ? 1.f : 0.f;
-        bool knows = fired != 0.f;
-        uint32_t los = 0;
-        if (alive) {
-            const int jm0 = l0 + (team ^ 1) * T;
-            for (int mm = 0; mm < T; mm++) los |= ((st.i(kOsVis, jm0 + mm) >> off) & 1u) << mm;
-            knows = knows || los != 0;
-        }
-        float cm[MPENV_FT_ENEMY_DIM]; // the common block, then the enemy tail
-        cm[0] = 1.f;
-        for (int k = 0; k < kMaxTeamSize; k++) cm[1 + k] = k == off ? 1.f : 0.f;
-        for (int k = 7; k < MPENV_FT_COMMON_DIM; k++) cm[k] = 0.f;
-        float ext[4] = { 0.f, 0.f, 0.f, 0.f };
-        if (alive) {
-            cm[7] = 1.f;
-            const Vec3 np = normalizedPosUnclampedD(sc, st.pos(me));
-            cm[8] = np.x; cm[9] = np.y; cm[10] = np.z;
-            cm[11] = 0.5f * ((st.f(kOsYaw, me) / kPi) + 1.f);
-            cm[12] = 0.5f * (st.f(kOsPitch, me) / (0.25f * kPi) + 1.f);
-            cm[13] = st.f(kOsVX, me); cm[14] = st.f(kOsVY, me); cm[15] = st.f(kOsVZ, me);
-            const int cp = st.i(kOsCurPose, me), tp = st.i(kOsTgtPose, me);
-            cm[16] = cp == kStand ? 1.f : 0.f;
-            cm[17] = cp == kCrouch ? 1.f : 0.f;
-            cm[18] = cp == kProne ? 1.f : 0.f;
-            cm[19] = tp == kStand ? 1.f : 0.f;
-            cm[20] = tp == kCrouch ? 1.f : 0.f;
-            cm[21] = tp == kProne ? 1.f : 0.f;
-            cm[22] = (float)st.i(kOsTrans, me) / (float)c::kPoseTransitionSpeed;
-            cm[23] = (st.i(kOsFlags, me) & kFlagInZone) ? 1.f : 0.f;
-            ext[0] = st.f(kOsHP, me) / 100.f;
-            ext[1] = (float)st.i(kOsMag0, me) / 30;
-            ext[2] = (float)st.i(kOsMag1, me);
-            ext[3] = float(st.i(kOsHeal, me)) / float(c::kOutOfCombatSteps);
-        }
-        cm[MPENV_FT_COMMON_DIM + 0] = alive ? (float)st.i(kOsShot, me) : 0.f;
-        cm[MPENV_FT_COMMON_DIM + 1] = fired;
-        for (int mm = 0; mm < kMaxTeamSize; mm++) cm[MPENV_FT_COMMON_DIM + 2 + mm] = (los >> mm) & 1u ? 1.f : 0.f;
-        cm[MPENV_FT_COMMON_DIM + 8] = knows ? 1.f : 0.f;
-        static_assert(MPENV_FT_ENEMY_DIM == MPENV_FT_COMMON_DIM + 9, "ft enemy tail");
-        // one staged row serves all three slots: the common block + enemy
-        // tail; the player tail is staged over the enemy tail after the
-        // enemy row has left
-        constexpr int P = kObsRowPad;
-        static_assert(MPENV_FT_ENEMY_DIM <= P && MPENV_FT_PLAYER_DIM <= P, "ft rows");
-        static_assert(MPENV_FT_COMMON_DIM % 4 == 0 && MPENV_FT_PLAYER_DIM % 4 == 0, "16-B ft rows");
-        const uint64_t all = __ballot(true), zlk = __ballot(!knows);
-        for (int h = 0; h < hs.halves(); h++) {
-            hs.stage<P>(h, cm, MPENV_FT_ENEMY_DIM);
-            hs.stageOff(h, (theirs * 6 + off) * MPENV_FT_ENEMY_DIM);
-            waveSync();
-            hs.flushOff<MPENV_FT_ENEMY_DIM, P>(h, S.ftEnemies, all, 0ull);
-            waveSync();
-            hs.stage<P>(h, ext, 4, MPENV_FT_COMMON_DIM);
-            hs.stageOff(h, (theirs * 6 + off) * MPENV_FT_COMMON_DIM);
-            waveSync();
-            hs.flushOff4<MPENV_FT_COMMON_DIM / 4, P>(h, S.ftLastKnown, all, zlk);
-            waveSync();
-            hs.stageOff(h, (mine * 6 + off) * MPENV_FT_PLAYER_DIM);
-            waveSync();
-            hs.flushOff4<MPENV_FT_PLAYER_DIM / 4, P>(h, S.ftPlayers, all, 0ull);
-            waveSync();
-        }
-    }
-}
-
-// pvpLidarSystem (sim.cpp:3324-3506).  Lane = ray.  Rays are dealt to
-// waves in units of 4 agents = 5 wave tasks: tasks 0-3 carry one agent's 64
-// forward rays each (32 angles x 2 heights, one origin and a narrow fan, so
-// the wave's lanes walk similar BVH paths), task 4 the 4 agents' 16 rear rays.
-// Against 64 consecutive rays of the flat [agent][80] order (which straddle
-// two agents in 4 of 5 waves) this cuts the wave-lockstep node iterations by
-// ~12% and triangle tests by ~19% (tools/trav_stats.cpp on recorded rays);
-// every lane's arithmetic is unchanged.  A block owns `iters` x 16
-// consecutive tasks and its 16 waves draw them one at a time from a counter
-// in LDS, so a wave that drew short tasks takes more of them and the block's
-// LDS image is not held for the wave with the longest fixed share (DESIGN.md
-// §4, "k_lidar's task scheduling").  `iters` is up to kLidarItersAuto (amortises the BVH staging) on big
-// batches, fewer on small ones so the grid still spreads over the CUs (at 64
-// worlds 1v1 a fixed 8 put the whole lidar on 5 CUs): lidarItersFor.
-constexpr int kLidarIters = 12;    // compiled maximum of tasks per wave (mpenv_set_lidar_iters)
-constexpr int kLidarItersAuto = 6; // what launchLidar's caller gets on big batches: round 5, one world group: 4: 0.665, 5: 0.642, 6: 0.643 ms steady (profiles/r05m_lab_lidar_iters.jsonl; round 2: 1: 0.98, 2: 0.91, 4: 0.89, 8: 0.92 ms)
-// 1024-thread blocks: the 8 octant node images + the three rotated vertex
-// copies (31 + 36 KB on simple_map) are staged once per 16 waves, so 2
-// blocks per CU (8 waves per SIMD) fit the 160 KB of LDS: 67 KB of image
-// plus 9,168 B of static LDS (the agent stage, sized for kLidarIters = 12
-// tasks per wave: 8,832 B; 5,376 B when the maximum was 6) is ~76 KB per
-// block, 152 KB for two, 8 KB of headroom.
-constexpr int kLidarBlock = 1024;
-constexpr int kLidarWaves = kLidarBlock / 64;
-constexpr int kLidarStageMax = 184, kLidarStageCols = 12; // k_lidar's per-block agent stage
-static_assert(4 * ((kLidarIters * kLidarWaves) / 5 + 2) + 2 * (2 * kMaxTeamSize - 1) <= kLidarStageMax,
-              "k_lidar agent stage");
-
-__device__ __host__ __forceinline__ int64_t lidarTasks(int64_t A) { return ((A + 3) / 4) * 5; }
-
-// 8 waves per SIMD (64 VGPRs, a few bytes of spill outside the traversal
-// loop): latency-bound LDS traversal gains more from occupancy (-7%).
-#define MP_LIDAR_ATTR __attribute__((amdgpu_waves_per_eu(8)))
-
-// Maximum over the lane's DPP row (16 lanes) of non-negative float bit
-// patterns compared as signed ints (the float order; -0 sorts lowest): the
-// exact float maximum of the row's hit distances, without LDS round trips.
-__device__ __forceinline__ int rowMaxBits16(int v)
-{
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false));  // quad_perm [1, 0, 3, 2]
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));  // quad_perm [2, 3, 0, 1]
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false)); // row_ror:4
-    return max(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false)); // row_ror:8
-}
-
-template <class LBVH>
-__device__ __forceinline__ void lidarBody(const DevState &S, const SceneDev &sc, int iters, char *img)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // Ray-fan directions (sim.cpp:3324-3506): theta depends only on the ray
-    // slot, so the 32 forward + 8 rear (-cos, sin) pairs are computed once
-    // per workgroup with the same sinf_/cosf_ and read from LDS.
-    __shared__ float2 fan[32 + 8];
-    if (threadIdx.x < 40) {
-        const bool fwd = threadIdx.x < 32;
-        const int x = fwd ? threadIdx.x : threadIdx.x - 32;
-        const int width = fwd ? 32 : 8;
-        const float range = fwd ? 0.75f * kPi : -kPi;
-        const float offset = fwd ? 0.5f * (1.f - 0.75f) * kPi : 0.f;
-        const float theta = range * (float(x) / float(width - 1)) + offset;
-        fan[threadIdx.x] = make_float2(-cosf_(theta), sinf_(theta));
-    }
-    const uint32_t N = (uint32_t)S.N, T = (uint32_t)S.T;
-    const uint32_t A = (uint32_t)S.A;
-    const uint32_t ntasks = (uint32_t)lidarTasks(S.A);
-    // The agents this block's tasks read -- the rays' origins and frames and
-    // every capsule of their worlds -- staged in LDS with the BVH: whole
-    // worlds around the block's task range (at kLidarIters = 12: <= 40 units
-    // of 4 agents plus a partial world at each end: <= 182 agents, N <= 12;
-    // the automatic 6: <= 21 units, <= 106 agents), so no task waits on HBM
-    // for them.
-    __shared__ float agentStage[kLidarStageCols][kLidarStageMax];
-    const uint32_t t0 = xcdBlockId() * (uint32_t)iters * kLidarWaves;
-    const uint32_t t1 = min(ntasks, t0 + (uint32_t)iters * kLidarWaves);
-    uint32_t s0 = 0, ns = 0;
-    if (t0 < t1) {
-        const uint32_t a_lo = (t0 / 5u) * 4u, a_hi = min(A, ((t1 - 1u) / 5u) * 4u + 4u);
-        s0 = (a_lo / N) * N;
-        ns = ((a_hi - 1u) / N + 1u) * N - s0;
-        for (uint32_t k = threadIdx.x; k < ns; k += blockDim.x) {
-            const uint32_t g = s0 + k;
-            agentStage[0][k] = S.px[g];
-            agentStage[1][k] = S.py[g];
-            agentStage[2][k] = S.pz[g];
-            agentStage[3][k] = S.aw[g];
-            agentStage[4][k] = S.ax[g];
-            agentStage[5][k] = S.ay[g];
-            agentStage[6][k] = S.az[g];
-            agentStage[7][k] = S.rw[g];
-            agentStage[8][k] = S.rx[g];
-            agentStage[9][k] = S.ry[g];
-            agentStage[10][k] = S.rz[g];
-            agentStage[11][k] = viewHeightD(S.curPose[g]);
-        }
-    }
-    // gpuStreamStep's caller buffers (engine.h OutTab), read once per block
-    // into wave-uniform values (off: all null), held in scalar registers
-    // across the traversals
-    float4 *oFwd = nullptr, *oRear = nullptr, *oMap0 = nullptr, *oMap1 = nullptr;
-    if (S.outTab && S.outTab->on) {
-        auto uniform = [](const float *p) {
-            const uint64_t v = reinterpret_cast<uint64_t>(p);
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-            return reinterpret_cast<float4 *>(((uint64_t)hi << 32) | lo);
-        };
-        oFwd = uniform(S.outTab->fwdLidar);
-        oRear = uniform(S.outTab->rearLidar);
-        oMap0 = uniform(S.outTab->agentMap0);
-        oMap1 = uniform(S.outTab->agentMap1);
-    }
-    // The block's tasks are dealt from this counter: wave v starts with task
-    // v of the block; a wave that is free draws the next one (one LDS atomic
-    // by lane 0, broadcast), and leaves when the range is used up.  No wave
-    // ever waits for another.  With one task per wave nothing is drawn.
-    __shared__ uint32_t nextTask;
-    if (threadIdx.x == 0) nextTask = kLidarWaves;
-    const LBVH bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img, sc); // ends with __syncthreads
-    auto draw = [&]() {
-        if (iters == 1) return (uint32_t)kLidarWaves;
-        // the lane id read here (volatile, as in the loop body): hoisted out
-        // of the loop it lived across the traversal and was spilled
-        uint32_t ln, drawn = 0u;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-        if (ln == 0u) drawn = atomicAdd(&nextTask, 1u);
-        return (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn);
-    };
-    for (uint32_t k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); t0 + k < t1; k = draw()) {
-        const uint32_t task = t0 + k; // wave-uniform
-        const uint32_t unit = task / 5u, sub = task - unit * 5u;
-        const bool fwd = sub < 4u;
-        // The ray of lane `ln`: a tail unit's lanes past A trace a copy of
-        // the last agent's rays and store nothing.
-        auto rayIndex = [&](uint32_t ln, uint32_t &g, bool &valid, uint32_t &kk) {
-            const uint32_t g_raw = unit * 4u + (fwd ? sub : (ln >> 4));
-            valid = g_raw < A;
-            g = min(g_raw, A - 1u); // (a min with a scalar: a select kept A - 1 in a VGPR across the loop)
-            kk = fwd ? ln : (ln & 15u); // ray slot within the forward / rear fan
-        };
-        auto makeRay = [&](uint32_t ln, uint32_t &g, bool &valid, uint32_t &kk, Vec3 &ray_o, Vec3 &dir) {
-            rayIndex(ln, g, valid, kk);
-            const uint32_t h = fwd ? (kk >> 5) : (kk >> 3), x = fwd ? (kk & 31u) : (kk & 7u);
-            const uint32_t k = g - s0, qc = fwd ? 3u : 7u;
-            const Quat q = quat(agentStage[qc][k], agentStage[qc + 1u][k], agentStage[qc + 2u][k],
-                                agentStage[qc + 3u][k]);
-            const Vec3 dir_fwd = rotateVec(q, kFwd);
-            const Vec3 dir_right = rotateVec(q, kRight);
-            const float top = agentStage[11][k] + c::kAgentRadius;
-            ray_o = v3(agentStage[0][k], agentStage[1][k], agentStage[2][k]);
-            ray_o.z += c::kAgentRadius + (top - 2.f * c::kAgentRadius) * (float(h) / float(2 - 1));
-            const float2 cs = fan[fwd ? x : 32 + x];
-            dir = normalize(cs.x * dir_right + cs.y * dir_fwd);
-        };
-        // Lane id read inside the loop (volatile: not hoisted), so the
-        // lane-derived offsets are formed per task instead of living as
-        // loop invariants across the traversal, which at 64 VGPRs the
-        // compiler would spill to scratch.
-        uint32_t lane;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-        uint32_t g, kk;
-        bool valid;
-        Vec3 ray_o, dir;
-        // The BVH first (one traversal for both fan kinds), then the world's
-        // capsules.  World / agent indices are formed after the traversal,
-        // from an opaque copy of g (nothing but the ray lives across it).
-        float tb;
-        bool bhit;
-        {
-            makeRay(lane, g, valid, kk, ray_o, dir);
-            // the ray's octant image: same nodes and leaves, near-first slot
-            // order (scene.h octantNodeImages)
-            LBVH ob = bvh;
-            ob.nodes = reinterpret_cast<const MP_LDS BVHNode *>(reinterpret_cast<const MP_LDS uint4 *>(bvh.nodes) +
-                                                                 rayOctant(dir) * sc.numLidarNodes * kOctNodeQ);
-            bhit = bvhTraceRayT<false, kOctNodeQ, true, true>(ob, ray_o, dir, tb, kFltMax, 0.f);
-        }
-        // The lane id again (volatile) and the ray's indices from it: integer
-        // work only, so they need not live across the traversal (at 64 VGPRs
-        // they were spilled to scratch).  Shuffles below address lanes from
-        // this id too (ds_bpermute), not from a lane id kept for the kernel.
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-        rayIndex(lane, g, valid, kk);
-        auto shflLane = [](float v, uint32_t src) {
-            return __int_as_float(__builtin_amdgcn_ds_bpermute((int)(src << 2), __float_as_int(v)));
-        };
-        const uint32_t w = __umulhi(g, S.nMagic); // g / N (engine.h)
-        const uint32_t i = g - w * N;
-        const int64_t g0 = (int64_t)w * N;
-        WorldHit hw;
-        if (fwd) {
-            // Forward fan (one agent, one xy origin per wave): the BVH first,
-            // then only the capsules some ray of the wave could hit before
-            // its BVH hit.  Any point of capsule j lies within r of its
-            // vertical axis, so a ray entering it at t has t >= d_xy - r
-            // (d_xy = xy distance from the origin to the axis); a capsule
-            // with d_xy - 1.01 r - 1 > max over the wave's rays of the BVH
-            // hit t can enter no ray's `t < min_hit_t` (utils.cpp:57-69) and
-            // is dropped for the whole wave (the margin dwarfs the rounding
-            // of t ~ 1e-3 at these distances).  Lane j < N loads capsule j
-            // once; the per-ray loop reads the survivors' bases from those
-            // lanes (readlane) in ascending j, so ties resolve as before.
-            float min_t = bhit ? tb : kFltMax;
-            const int rm = rowMaxBits16(__float_as_int(min_t));
-            const float mx = __int_as_float(max(max(__builtin_amdgcn_readlane(rm, 0), __builtin_amdgcn_readlane(rm, 16)),
-                                                max(__builtin_amdgcn_readlane(rm, 32), __builtin_amdgcn_readlane(rm, 48))));
-            float cx = 0.f, cy = 0.f, cz = 0.f;
-            bool keep = false;
-            if (lane < N) {
-                const uint32_t k = (uint32_t)(g0 - s0) + lane;
-                cx = agentStage[0][k]; cy = agentStage[1][k]; cz = agentStage[2][k];
-                const float dx = cx - ray_o.x, dy = cy - ray_o.y;
-                keep = lane != i && !(sqrtf(dx * dx + dy * dy) - c::kAgentRadius * 1.01f - 1.f > mx);
-            }
-            uint64_t cm = __ballot(keep);
-            bool hit = bhit;
-            int ent = -1;
-            const float dxy2 = dir.x * dir.x + dir.y * dir.y;
-            const float cull_r2 = (kCapsuleRadius * 1.01f) * (kCapsuleRadius * 1.01f);
-            while (cm) {
-                const int j = __builtin_ctzll(cm);
-                cm &= cm - 1;
-                Vec3 co = v3(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cx), j)),
-                             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cy), j)),
-                             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cz), j)));
-                co.z += kCapsuleRadius;
-                const Vec3 tr = ray_o - co;
-                // the per-ray conservative culls of capsulesD
-                const float cr = tr.x * dir.y - tr.y * dir.x;
-                if (cr * cr > cull_r2 * dxy2) continue;
-                const float along = -(tr.x * dir.x + tr.y * dir.y + tr.z * dir.z);
-                const float ahead = along + fmaxD(0.f, kCapsuleSegment * dir.z) + kCapsuleRadius * 1.01f;
-                if (ahead < 0.f) continue;
-                if (along + fminD(0.f, kCapsuleSegment * dir.z) - kCapsuleRadius * 1.01f > min_t) continue;
-                const float t = intersectRayZOriginCapsule(tr, dir, kCapsuleRadius, kCapsuleSegment);
-                if (t != 0 && t < min_t) {
-                    min_t = t;
-                    hit = true;
-                    ent = j;
-                }
-            }
-            hw.hit = hit;
-            hw.t = min_t;
-            hw.entity = ent;
-        } else {
-            // Rear fans: the same cull per 16-lane group (one agent, one xy
-            // origin per group; N <= 12 capsules).  Lane q*16 + j < q*16 + N
-            // loads capsule j of group q's world; the wave walks the union
-            // of the groups' surviving j in ascending order and each lane
-            // takes its group's copy (ds_bpermute) and tests only the j its
-            // group kept -- per ray the same capsules in the same order as
-            // capsulesD minus those no ray of the group can reach.
-            float min_t = bhit ? tb : kFltMax;
-            const float mx = __int_as_float(rowMaxBits16(__float_as_int(min_t)));
-            const uint32_t gb = lane & 48u, jl = lane & 15u;
-            float cx = 0.f, cy = 0.f, cz = 0.f;
-            bool keep = false;
-            if (jl < N) {
-                const uint32_t k = (uint32_t)(g0 - s0) + jl;
-                cx = agentStage[0][k]; cy = agentStage[1][k]; cz = agentStage[2][k];
-                const float dx = cx - ray_o.x, dy = cy - ray_o.y;
-                keep = jl != i && !(sqrtf(dx * dx + dy * dy) - c::kAgentRadius * 1.01f - 1.f > mx);
-            }
-            const uint64_t cm = __ballot(keep);
-            uint32_t um = (uint32_t)((cm | (cm >> 16) | (cm >> 32) | (cm >> 48)) & 0xffffu);
-            const uint32_t mine = (uint32_t)(cm >> gb) & 0xffffu;
-            // the four agents in one world (always for 6v6: 4 divides N):
-            // every group holds the same capsules, read from group 0's lanes
-            const bool oneWorld = __ballot(w != (uint32_t)__builtin_amdgcn_readfirstlane((int)w)) == 0ull;
-            bool hit = bhit;
-            int ent = -1;
-            const float dxy2 = dir.x * dir.x + dir.y * dir.y;
-            const float cull_r2 = (kCapsuleRadius * 1.01f) * (kCapsuleRadius * 1.01f);
-            while (um) {
-                const int j = __builtin_ctz(um);
-                um &= um - 1u;
-                Vec3 co;
-                if (oneWorld) {
-                    co = v3(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cx), j)),
-                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cy), j)),
-                            __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cz), j)));
-                } else {
-                    const uint32_t src = gb + (uint32_t)j;
-                    co = v3(shflLane(cx, src), shflLane(cy, src), shflLane(cz, src));
-                }
-                if (!((mine >> j) & 1u)) continue;
-                co.z += kCapsuleRadius;
-                const Vec3 tr = ray_o - co;
-                const float cr = tr.x * dir.y - tr.y * dir.x;
-                if (cr * cr > cull_r2 * dxy2) continue;
-                const float along = -(tr.x * dir.x + tr.y * dir.y + tr.z * dir.z);
-                const float ahead = along + fmaxD(0.f, kCapsuleSegment * dir.z) + kCapsuleRadius * 1.01f;
-                if (ahead < 0.f) continue;
-                if (along + fminD(0.f, kCapsuleSegment * dir.z) - kCapsuleRadius * 1.01f > min_t) continue;
-                const float t = intersectRayZOriginCapsule(tr, dir, kCapsuleRadius, kCapsuleSegment);
-                if (t != 0 && t < min_t) {
-                    min_t = t;
-                    hit = true;
-                    ent = j;
-                }
-            }
-            hw.hit = hit;
-            hw.t = min_t;
-            hw.entity = ent;
-        }
-        if (!valid) continue;
-        const bool second = i >= T; // team of the casting agent
-        float4 out;
-        if (hw.hit) {
-            const bool wall = hw.entity == -1;
-            const bool tm = !wall && ((uint32_t)hw.entity >= T) == second;
-            out = make_float4(fminD(hw.t, sc.maxDist), wall ? 1.f : 0.f, tm ? 1.f : 0.f, (!wall && !tm) ? 1.f : 0.f);
-        } else {
-            out = make_float4(-1.f, 0.f, 0.f, 0.f);
-        }
-        // Addresses formed after the traversal (nothing but the ray lives
-        // across it, so 64 VGPRs hold the loop without scratch spills).
-        float4 *dst = fwd ? reinterpret_cast<float4 *>(S.fwdLidar) + (int64_t)g * kFwdRays + kk
-                          : reinterpret_cast<float4 *>(S.rearLidar) + (int64_t)g * kRearRays + kk;
-        const int64_t slot = ((int64_t)w * 2 + (second ? 1 : 0)) * kMaxTeamSize + (second ? i - T : i);
-        float4 *tdst = fwd ? reinterpret_cast<float4 *>(S.ftFwdLidar) + slot * kFwdRays + kk
-                           : reinterpret_cast<float4 *>(S.ftRearLidar) + slot * kRearRays + kk;
-        // fullTeamObservationsSystem copies the lidar before this system
-        // overwrites it (sim.cpp:5283-5310): the previous value moves into
-        // the team interface's slot.  (Moving this copy into a block
-        // prologue, so that the loop loads nothing, measured slower:
-        // DESIGN.md §4, "k_lidar's task scheduling".)
-        *tdst = *dst;
-        *dst = out;
-        // gpuStreamStep: the caller's lidar buffer too (the engine's copy is
-        // state: the bots and the next full-team copy read it), and the
-        // agent's two agent maps zero-filled by its forward wave (4 KB each:
-        // 4 store instructions of 64 x 16 B per map, no loads; the stores
-        // drain while the wave's next traversal runs)
-        if (oFwd) {
-            const int64_t gb = S.outBase + (int64_t)g;
-            float4 *cdst = fwd ? oFwd + gb * kFwdRays + kk : oRear + gb * kRearRays + kk;
-            *cdst = out;
-            if (fwd) {
-                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 *m0 = oMap0 + gb * 256 + kk;
-                float4 *m1 = oMap1 + gb * 256 + kk;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    m0[64 * q] = z;
-                    m1[64 * q] = z;
-                }
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar(DevState S, SceneDev sc, int iters)
-{
-    lidarBody<LBVHL>(S, sc, iters, nullptr);
-}
-
-__global__ void __launch_bounds__(kLidarBlock) MP_LIDAR_ATTR k_lidar_g(DevState S, SceneDev sc, int iters, SceneImages img)
-{
-    lidarBody<LBVHG>(S, sc, iters, img.oct);
-}
-
 // The global-resident images, once per scene upload: one block runs the
 // staging loops of stageBVHSphere (whose image begins with stageBVH's) and
 // stageBVHOct into the two buffers, so the bytes are those a block of the
@@ -4331,283 +2351,6 @@ __global__ void __launch_bounds__(kBlock) k_scene_images(SceneDev sc, SceneImage
 {
     (void)stageBVHSphere<LBVHG, true>(img.sphere, sc);
     (void)stageBVHOct<LBVHG, true>(img.oct, sc);
-}
-
-static int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
-
-// Debug/test hook: closest-hit BVH queries for caller rays (mode 0 = the
-// traversal inlined into the step kernels, 1 = its out-of-line copy).
-template <class LBVH>
-__device__ __forceinline__ void traceRaysBody(const SceneDev &sc, const float *o, const float *d, int n, int mode,
-                                              float *t_out, int32_t *hit_out, char *img)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const LBVH bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img, sc);
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const Vec3 org = v3(o[3 * r], o[3 * r + 1], o[3 * r + 2]);
-    const Vec3 dir = v3(d[3 * r], d[3 * r + 1], d[3 * r + 2]);
-    float t = 0.f;
-    bool hit;
-    if (mode == 0) {
-        hit = bvhTraceRayD(bvh, org, dir, t); // inlined, as in the step kernels
-    } else {
-        RayHitD h = bvhTraceRayExactD(bvh, org, dir);
-        hit = h.hit != 0;
-        t = h.t;
-    }
-    t_out[r] = hit ? t : 0.f;
-    hit_out[r] = hit ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(kBlock) k_trace_rays(SceneDev sc, const float *o, const float *d, int n, int mode,
-                                                       float *t_out, int32_t *hit_out)
-{
-    traceRaysBody<LBVHL>(sc, o, d, n, mode, t_out, hit_out, nullptr);
-}
-
-__global__ void __launch_bounds__(kBlock) k_trace_rays_g(SceneDev sc, const float *o, const float *d, int n, int mode,
-                                                         float *t_out, int32_t *hit_out, SceneImages img)
-{
-    traceRaysBody<LBVHG>(sc, o, d, n, mode, t_out, hit_out, img.sphere);
-}
-
-int launchTraceRays(const SceneDev &sc, const SceneImages &img, const float *o, const float *d, int n, int mode,
-                    float *t, int32_t *hit, void *stream)
-{
-    if (n <= 0) return 0;
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_trace_rays_g, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, sc,
-                           o, d, n, mode, t, hit, img);
-    else
-        hipLaunchKernelGGL(k_trace_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), bvhLdsBytes(sc),
-                           (hipStream_t)stream, sc, o, d, n, mode, t, hit);
-    return check(hipGetLastError());
-}
-
-// Test hook (mpenv_debug_geom_queries, include/mpenv.h): one geometry query
-// per thread through the step kernels' own device functions, on the image
-// (LDS- or global-resident, as the step kernels' own) of the kernel each mode
-// stands in for (k_lidar / k_sim / k_vis / k_move).
-// The functions are force-inlined, so this is a second compilation of them:
-// it checks their shortcut arguments on chosen inputs, not the step kernels'
-// code generation (whole-step parity covers that).
-template <int kMode, class LBVH>
-__device__ __forceinline__ void geomQueriesBody(const SceneDev &sc, const mpenv_geom_queries &q, int n,
-                                                const SceneImages &img)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    LBVH bvh;
-    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img.oct, sc);
-    else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
-    else if constexpr (kMode == MPENV_GEOM_SIGHT) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
-    else bvh = stageBVHSphere<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const Vec3 org = v3(q.o[3 * r], q.o[3 * r + 1], q.o[3 * r + 2]);
-    const Vec3 dir = v3(q.d[3 * r], q.d[3 * r + 1], q.d[3 * r + 2]);
-    const int N = q.num_caps;
-    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) {
-        // as k_lidar forms `ob`
-        LBVH ob = bvh;
-        ob.nodes = reinterpret_cast<const MP_LDS BVHNode *>(reinterpret_cast<const MP_LDS uint4 *>(bvh.nodes) +
-                                                             rayOctant(dir) * sc.numLidarNodes * kOctNodeQ);
-        float tb;
-        const bool hit = bvhTraceRayT<false, kOctNodeQ, true, true>(ob, org, dir, tb, kFltMax, 0.f);
-        q.t[r] = tb;
-        q.i0[r] = hit ? 1 : 0;
-    } else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) {
-        float cx[12], cy[12], cz[12]; // the query's world as position columns
-        for (int j = 0; j < N; j++) {
-            const float *cp = q.caps + ((size_t)r * N + j) * 3;
-            cx[j] = cp[0]; cy[j] = cp[1]; cz[j] = cp[2];
-        }
-        const WorldHit h = traceWorldD(bvh, cx, cy, cz, 0, N, org, dir, q.sel[r]);
-        q.i0[r] = h.hit ? 1 : 0;
-        q.t[r] = h.t;
-        q.i1[r] = h.entity;
-    } else if constexpr (kMode == MPENV_GEOM_SIGHT) {
-        const int target = q.sel[r];
-        bool seen;
-        if (q.sub == 0) {
-            // k_vis phase B: B1 on every ray, B2 on the unresolved ones
-            const uint32_t numTris = (uint32_t)(sc.numVerts / 3);
-            const bool hints = numTris < 0xffffu;
-            auto capsule = [&](int j) {
-                const float *cp = q.caps + ((size_t)r * N + j) * 3;
-                return v3(cp[0], cp[1], cp[2]);
-            };
-            float t_c;
-            seen = false;
-            if (!visibleQuickD(bvh, capsule, org, dir, target, hints ? q.hint + r : nullptr, numTris, t_c))
-                seen = visibleFullD(bvh, capsule, N, org, dir, target, t_c, hints ? q.hint + r : nullptr);
-        } else {
-            float cx[12], cy[12], cz[12];
-            for (int j = 0; j < N; j++) {
-                const float *cp = q.caps + ((size_t)r * N + j) * 3;
-                cx[j] = cp[0]; cy[j] = cp[1]; cz[j] = cp[2];
-            }
-            seen = visibleRayD(bvh, cx, cy, cz, 0, N, org, dir, target);
-        }
-        q.i0[r] = seen ? 1 : 0;
-    } else if constexpr (kMode == MPENV_GEOM_CASTS) {
-        if (q.sub == 2) {
-            SphereHit h0, h1;
-            h1.t = kFltMax;
-            h1.n = v3(0.f, 0.f, 0.f);
-            castNear2D(bvh, sc, org, q.z1[r], dir, q.bound[r], q.sel[r] != 0, h0, h1);
-            q.t[2 * r] = h0.t;
-            q.t[2 * r + 1] = h1.t;
-            float *np = q.normal + (size_t)r * 6;
-            np[0] = h0.n.x; np[1] = h0.n.y; np[2] = h0.n.z;
-            np[3] = h1.n.x; np[4] = h1.n.y; np[5] = h1.n.z;
-        } else if (q.sub == 3) {
-            q.t[r] = castFirstNearD(bvh, sc, org, dir, q.bound[r]);
-        } else {
-            const SphereHit h = q.sub == 0 ? bvhSphereCastD(bvh, org, dir, kSphereR)
-                                           : castNearD(bvh, sc, org, dir, q.bound[r]);
-            q.t[r] = h.t;
-            q.normal[3 * r] = h.n.x; q.normal[3 * r + 1] = h.n.y; q.normal[3 * r + 2] = h.n.z;
-        }
-    } else {
-        // applyVelocityD's call: lanes that left k_move early are gone, the
-        // rest call with or without `need`
-        const int flags = q.sel[r];
-        if (!(flags & 1)) return;
-        float hd4[4];
-        for (int k = 0; k < 4; k++) hd4[k] = q.t[4 * r + k];
-        stuckCastsD(bvh, (flags & 2) != 0, org, dir, q.bound[r], hd4);
-        for (int k = 0; k < 4; k++) q.t[4 * r + k] = hd4[k];
-    }
-}
-
-template <int kMode>
-__global__ void __launch_bounds__(kBlock) k_geom_queries(SceneDev sc, mpenv_geom_queries q, int n)
-{
-    geomQueriesBody<kMode, LBVHL>(sc, q, n, SceneImages {});
-}
-
-template <int kMode>
-__global__ void __launch_bounds__(kBlock) k_geom_queries_g(SceneDev sc, mpenv_geom_queries q, int n, SceneImages img)
-{
-    geomQueriesBody<kMode, LBVHG>(sc, q, n, img);
-}
-
-int launchGeomQueries(const SceneDev &sc, const SceneImages &img, int mode, int n, const mpenv_geom_queries &q,
-                      void *stream)
-{
-    if (n <= 0) return 0;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (img.residency == kResidencyGlobal) {
-        switch (mode) {
-        case MPENV_GEOM_LIDAR_RAY:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_LIDAR_RAY>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_WORLD_RAY:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_WORLD_RAY>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_SIGHT:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_SIGHT>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_CASTS:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_CASTS>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_STUCK:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_STUCK>, grid, block, 0, st, sc, q, n, img);
-            break;
-        default:
-            return -1;
-        }
-        return check(hipGetLastError());
-    }
-    switch (mode) {
-    case MPENV_GEOM_LIDAR_RAY:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_LIDAR_RAY>, grid, block, bvhLdsBytesOct(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_WORLD_RAY:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_WORLD_RAY>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_SIGHT:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_SIGHT>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_CASTS:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_CASTS>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_STUCK:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_STUCK>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
-        break;
-    default:
-        return -1;
-    }
-    return check(hipGetLastError());
-}
-
-// Debug gather of internal state into the MPENV_EXPORT_DEBUG_* layouts.
-__global__ void __launch_bounds__(256) k_debug(DevState S, float *af, int32_t *ai, int32_t *wi, float *wf,
-                                               uint32_t *explore, float *crumbs)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < S.A) {
-        const int64_t g = t;
-        float *f = &af[g * MPENV_DBG_AF_COUNT];
-        f[0] = S.px[g]; f[1] = S.py[g]; f[2] = S.pz[g];
-        f[3] = S.vx[g]; f[4] = S.vy[g]; f[5] = S.vz[g];
-        f[6] = S.rw[g]; f[7] = S.rx[g]; f[8] = S.ry[g]; f[9] = S.rz[g];
-        f[10] = S.ayaw[g]; f[11] = S.apitch[g];
-        f[12] = S.aw[g]; f[13] = S.ax[g]; f[14] = S.ay[g]; f[15] = S.az[g];
-        f[16] = S.maxVel[g]; f[17] = S.minDistZone[g]; f[18] = S.firedT[g]; f[19] = S.bcPenalty[g];
-        f[20] = S.sx[g]; f[21] = S.sy[g]; f[22] = S.sz[g];
-        f[23] = S.minDistSub[g];
-        int32_t *n = &ai[g * MPENV_DBG_AI_COUNT];
-        n[0] = S.curPose[g]; n[1] = S.tgtPose[g]; n[2] = S.transRem[g];
-        n[3] = S.rngA[g]; n[4] = S.rngB[g]; n[5] = S.rngCtr[g];
-        n[6] = S.landedOn[g]; n[7] = S.respawnSteps[g]; n[8] = S.autohealSteps[g];
-        n[9] = S.flags[g] & 63;
-        n[10] = S.wasShot[g]; n[11] = S.weapon[g]; n[12] = S.bcLast[g]; n[13] = S.bcSteps[g];
-        n[14] = S.visMask[g];
-        n[15] = S.newCells[g];
-        if (explore) {
-            // 1 = visited in the agent's current episode (the reference's
-            // tag == curEpisodeIdx), 0 otherwise
-            const bool cur = S.exploreEp[g] == S.episode[g / S.N];
-            const int ct = S.exploreTile[g];
-            const uint64_t cw = (uint64_t)(uint32_t)S.exploreLo[g] | ((uint64_t)(uint32_t)S.exploreHi[g] << 32);
-            for (int k = 0; k < kGridCells; k++) {
-                const int cy = k / kGridW, cx = k - cy * kGridW;
-                const int t = exploreTileD(cx, cy);
-                const uint64_t word = t == ct ? cw : S.exploreBits[g * kExploreTiles + t];
-                explore[g * kGridCells + k] = cur ? (uint32_t)((word >> exploreBitD(cx, cy)) & 1ull) : 0u;
-            }
-        }
-    }
-    if (t < S.W) {
-        const int w = (int)t;
-        int32_t *n = &wi[(int64_t)w * MPENV_DBG_WI_COUNT];
-        n[0] = S.teamA[w]; n[1] = S.curStep[w]; n[2] = S.finished[w]; n[3] = S.curZone[w];
-        n[4] = S.controlling[w]; n[5] = S.contested[w]; n[6] = S.captured[w]; n[7] = S.earned[w];
-        n[8] = S.zoneSteps[w]; n[9] = S.stepsUntilPoint[w]; n[10] = S.episode[w]; n[11] = S.episodeCounter[w];
-        n[12] = S.wRngA[w]; n[13] = S.wRngB[w]; n[14] = S.wRngCtr[w]; n[15] = S.numCrumbs[w];
-        n[16] = S.filtAct0[w]; n[17] = S.filtAct1[w]; n[18] = S.filtMatched0[w]; n[19] = S.filtMatched1[w];
-        n[20] = S.crumbOverflow[w];
-        n[21] = S.subState[w];
-        float *f = &wf[(int64_t)w * MPENV_DBG_WF_COUNT];
-        f[0] = S.teamRew0[w]; f[1] = S.teamRew1[w]; f[2] = S.goalMin0[w]; f[3] = S.goalMin1[w];
-        f[4] = S.goalTeam0[w]; f[5] = S.goalTeam1[w];
-        float *cdst = &crumbs[(int64_t)w * kMaxCrumbs * 8];
-        const float4 *cr = crumbPtr(S, w);
-        const int nc = S.numCrumbs[w];
-        for (int k = 0; k < kMaxCrumbs; k++) {
-            float *e = &cdst[k * 8];
-            if (k < nc) {
-                float4 p = cr[2 * k], meta = cr[2 * k + 1];
-                e[0] = p.x; e[1] = p.y; e[2] = p.z; e[3] = p.w;
-                e[4] = meta.x; e[5] = meta.y; e[6] = (float)__float_as_int(meta.z); e[7] = 1.f;
-            } else {
-                for (int q = 0; q < 8; q++) e[q] = 0.f;
-            }
-        }
-    }
 }
 
 // Copy one step of the action tape ([A][6] i32: 4 discrete + 2 aim) into the
@@ -4700,24 +2443,6 @@ size_t simLdsBytes(const SceneDev &sc, int32_t residency)
     return off + (size_t)(sc.numA + sc.numB + sc.numCommon) * sizeof(Spawn);
 }
 
-size_t moveLdsBytes(const SceneDev &sc, int32_t residency)
-{
-    return residency == kResidencyGlobal ? 0 : bvhLdsBytesSphere(sc);
-}
-
-size_t visLdsBytes(const SceneDev &sc, int32_t residency, int T)
-{
-    size_t stage = 0;
-    for (int t = T > 0 ? T : 1; t <= (T > 0 ? T : kMaxTeamSize); t++)
-        stage = std::max(stage, (size_t)kVisStageCols * 4 * visStageAgents(t, 2 * t));
-    return (residency == kResidencyGlobal ? 0 : bvhLdsBytes(sc)) + stage;
-}
-
-size_t lidarLdsBytes(const SceneDev &sc, int32_t residency)
-{
-    return residency == kResidencyGlobal ? 0 : bvhLdsBytesOct(sc);
-}
-
 int buildSceneImages(const SceneDev &sc, const SceneImages &img, void *stream)
 {
     hipLaunchKernelGGL(k_scene_images, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, sc, img);
@@ -4725,7 +2450,6 @@ int buildSceneImages(const SceneDev &sc, const SceneImages &img, void *stream)
     if (!rc) rc = check(hipStreamSynchronize((hipStream_t)stream));
     return rc;
 }
-static_assert(c::kAgentRadius == kSphereR, "k_move sphere casts use the agent radius (stageBVHSphere)");
 
 size_t bvhLdsBytesSphere(const SceneDev &sc)
 {
@@ -4754,28 +2478,6 @@ int launchResetOnly(const DevState &s, const SceneDev &sc, void *stream)
     return check(hipGetLastError());
 }
 
-int launchMove(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
-{
-    // Small batches (< 64 full blocks): one-wave blocks, so the few waves spread over CUs
-    // instead of sharing a CU's SIMDs (k_move is latency-bound: 5-7
-    // dependent sphere casts per lane).  Big batches keep 256-thread blocks
-    // (the 24 KB LDS image per block would otherwise cap occupancy).
-    // Agents per wave: 64 once the batch fills ~1.5 waves per SIMD (1,536
-    // waves on 256 CUs), else the power of two (>= 8) that gets closest.
-    int apw = 64;
-    while (apw > 8 && (s.A + apw - 1) / apw < 1536) apw >>= 1;
-    const int64_t waves = (s.A + apw - 1) / apw;
-    const int bs = waves < 64 * 4 ? 64 : kBlock;
-    const int64_t threads = waves * 64;
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_move_g, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, s,
-                           sc, apw, img);
-    else
-        hipLaunchKernelGGL(k_move, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), bvhLdsBytesSphere(sc),
-                           (hipStream_t)stream, s, sc, apw);
-    return check(hipGetLastError());
-}
-
 int launchSimStep(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
 {
     const int wpb = kSimBlock / s.N;
@@ -4786,34 +2488,6 @@ int launchSimStep(const DevState &s, const SceneDev &sc, const SceneImages &img,
     else
         hipLaunchKernelGGL(k_sim, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, kResidencyLds), (hipStream_t)stream,
                            s, sc);
-    return check(hipGetLastError());
-}
-
-int launchVisibility(const DevState &s, const SceneDev &sc, const SceneImages &img, void *stream)
-{
-    const int64_t waves = (s.A + (64 / s.T) - 1) / (64 / s.T);
-    const int blocks = (int)((waves * 64 + kBlock - 1) / kBlock);
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_vis_g, dim3(blocks), dim3(kBlock), visLdsBytes(sc, kResidencyGlobal, s.T),
-                           (hipStream_t)stream, s, sc, img);
-    else
-        hipLaunchKernelGGL(k_vis, dim3(blocks), dim3(kBlock),
-                           bvhLdsBytes(sc) + (size_t)kVisStageCols * 4 * visStageAgents(s.T, s.N),
-                           (hipStream_t)stream, s, sc);
-    return check(hipGetLastError());
-}
-
-int launchObservations(const DevState &s, const SceneDev &sc, void *stream)
-{
-    const int blocks = (int)((s.A + kObsBlock - 1) / kObsBlock);
-    hipLaunchKernelGGL(k_obs<false>, dim3(blocks), dim3(kObsBlock), 0, (hipStream_t)stream, s, sc, WireObs {});
-    return check(hipGetLastError());
-}
-
-int launchObservationsWire(const DevState &view, const SceneDev &sc, const WireObs &wo, void *stream)
-{
-    const int blocks = (int)((view.A + kObsBlock - 1) / kObsBlock);
-    hipLaunchKernelGGL(k_obs<true>, dim3(blocks), dim3(kObsBlock), 0, (hipStream_t)stream, view, sc, wo);
     return check(hipGetLastError());
 }
 
@@ -4833,41 +2507,6 @@ int computeZoneGoalTris(const SceneDev &sc, int32_t *dev_scratch, int32_t *host_
                                        (hipStream_t)stream));
     if (!rc) rc = check(hipStreamSynchronize((hipStream_t)stream));
     return rc;
-}
-
-int lidarItersMax() { return kLidarIters; }
-
-// k_lidar's automatic tasks per wave for a batch of A agents: ~1024 blocks
-// before the value grows past 1, so the grid still spreads over the CUs, and
-// kLidarItersAuto at most (C3 with the waves drawing their tasks: 6: 0.579 ms,
-// 10, the value with the fewest dispatch rounds on 256 CUs: 0.596 ms, DESIGN.md
-// §4; larger values are for mpenv_set_lidar_iters).
-int lidarItersFor(int64_t A)
-{
-    return (int)std::max<int64_t>(1, std::min<int64_t>(kLidarItersAuto, lidarTasks(A) / (kLidarWaves * 1024)));
-}
-
-int launchLidar(const DevState &s, const SceneDev &sc, const SceneImages &img, int iters, void *stream)
-{
-    if (iters < 1 || iters > kLidarIters) return -1; // the agent stage is sized for kLidarIters
-    const int64_t tasks = lidarTasks(s.A);
-    const int64_t per_block = (int64_t)kLidarWaves * iters;
-    const int blocks = (int)((tasks + per_block - 1) / per_block);
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_lidar_g, dim3(blocks), dim3(kLidarBlock), 0, (hipStream_t)stream, s, sc, iters, img);
-    else
-        hipLaunchKernelGGL(k_lidar, dim3(blocks), dim3(kLidarBlock), bvhLdsBytesOct(sc), (hipStream_t)stream, s, sc,
-                           iters);
-    return check(hipGetLastError());
-}
-
-int launchDebugGather(const DevState &s, float *af, int32_t *ai, int32_t *wi, float *wf, uint32_t *explore,
-                      float *crumbs, void *stream)
-{
-    const int64_t n = s.A > s.W ? s.A : s.W;
-    hipLaunchKernelGGL(k_debug, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, af, ai, wi,
-                       wf, explore, crumbs);
-    return check(hipGetLastError());
 }
 
 int launchFillActions(const DevState &s, const int32_t *src6, void *stream)

@@ -278,7 +278,7 @@ __device__ __forceinline__ bool wireOk(const DevState &S, const char *src, const
 //     worlds  thread = world: the message's episode counters, kept for the
 //             next message's reset test (double-buffered: next != prev);
 //     match   thread = 16 bytes of the [W][30] episode results, copied flat;
-//   k_obs_wire (kernels.hip) -- the observation rows, read straight from the
+//   k_obs_wire (obs.hip) -- the observation rows, read straight from the
 //     message's state columns (the shadow's own state columns are not
 //     written: round 5 stored ~90 B per agent there and k_obs read them
 //     back), with the last-known clear of a reset world folded in.

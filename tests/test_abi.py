@@ -265,6 +265,77 @@ def test_product_kernels_carry_no_lab_switches_and_lab_patches_apply(tmp_path):
             assert r.returncode == 0 and "fuzz" not in r.stdout, (p, q, r.stdout, r.stderr)
 
 
+CSRC = os.path.join(T.ROOT, "madrona-mp-env_amd", "csrc")
+
+
+def test_every_source_file_is_built():
+    """Every .hip / .cpp of csrc/ is a unit of libmpenv.so or one of the two
+    separately built programs: a new file cannot be forgotten."""
+    built = set(T.build_native.LIB_SOURCES) | {"pybind_module.cpp", "headless.cpp"}
+    found = {f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp"))}
+    assert found == built, (sorted(found - built), sorted(built - found))
+    assert len(T.build_native.LIB_SOURCES) == len(set(T.build_native.LIB_SOURCES))
+
+
+def _kernel_lab():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("kernel_lab", os.path.join(T.ROOT, "tools", "kernel_lab.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _ksim_body(text, head):
+    a = text.index(head) + len(head)
+    depth, k = 1, a
+    while depth:
+        depth += {"{": 1, "}": -1}.get(text[k], 0)
+        k += 1
+    return text[a:k - 1]
+
+
+def test_ksim_lab_hooks_apply(tmp_path):
+    """kernel_lab's k_sim hooks land in k_sim's body where it now is: one
+    phase timer per block barrier, every KSIM_SKIP phase behind its switch,
+    and the hooked file still compiles (device side, syntax only)."""
+    lab = _kernel_lab()
+    work = tmp_path / "src"
+    shutil.copytree(CSRC, work)
+    path = os.path.join(work, lab.KSIM_FILE)
+    before = _ksim_body(open(path).read(), lab.KSIM_HEAD)
+    barriers = before.count("__syncthreads();")
+    assert barriers > 0
+    lab.ksim_hooks(path)
+    hooked = open(path).read()
+    # "MP_PT()" also stands in the two #define lines of the prelude
+    assert hooked.count("MP_PT();") == barriers and hooked.count("__syncthreads(); MP_PT();") == barriers
+    for name, bit in lab.KSIM_SKIP:
+        calls = before.count(name)
+        assert calls >= 1, name
+        assert hooked.count(f"(MPENV_LAB_SIM_SKIP & {bit}) ? (void)0 : (void){name}") == calls, name
+    assert hooked.count("MPENV_LAB_SIM_SKIP &") == sum(before.count(name) for name, _ in lab.KSIM_SKIP)
+    B = T.build_native
+    cmd = B.compile_cmd(path, None, str(work), extra=["-DMPENV_LAB_PHASE_T", "-DMPENV_LAB_SIM_SKIP=1"],
+                        mode=("--cuda-device-only", "-fsyntax-only"))
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_ksim_lab_hooks_refuse_a_missing_anchor(tmp_path):
+    """With k_sim's body head gone from the copy the hooks raise instead of
+    leaving the kernel as it was."""
+    lab = _kernel_lab()
+    work = tmp_path / "src"
+    shutil.copytree(CSRC, work)
+    path = os.path.join(work, lab.KSIM_FILE)
+    text = open(path).read()
+    assert lab.KSIM_HEAD in text
+    open(path, "w").write(text.replace(lab.KSIM_HEAD, lab.KSIM_HEAD.replace("simBody", "simBodyMoved")))
+    with pytest.raises(ValueError, match="body head"):
+        lab.ksim_hooks(path)
+
+
 _XLA_CALL = r"""
 import ctypes as C, sys
 sys.path.insert(0, sys.argv[3])

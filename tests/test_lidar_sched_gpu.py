@@ -1,4 +1,4 @@
-"""k_lidar's task scheduling (csrc/kernels.hip): a block's waves draw its
+"""k_lidar's task scheduling (csrc/lidar.hip): a block's waves draw its
 tasks from a counter in LDS, the stream path's caller-buffer pointers are
 read once per block, and `iters` (wave tasks per wave of a block) is chosen
 per batch or forced with mpenv_set_lidar_iters.  None of it may change an

@@ -3,7 +3,7 @@
 (mesh_bvh.inl:1073-1104) returns t = 0 for any visited triangle with a vertex
 within the cast radius of 2·origin, so a bounded cast is only exact where no
 vertex lies that close.  k_move reads the grid below with the same float
-arithmetic as castQuirkFreeD (kernels.hip); this checks, on CPU, that every
+arithmetic as castQuirkFreeD (casts_dev.h); this checks, on CPU, that every
 point the guard calls clear is farther than the radius (plus slack) from
 every vertex in xy -- and so in 3-D -- including points hugging vertices and
 cell edges."""
@@ -93,7 +93,7 @@ def test_quirk_grid_covers_every_vertex_neighbourhood():
 
 KFLT_MAX = np.float32(np.finfo(np.float32).max)
 BUFFER = np.float32(0.05 * 15.0)
-CAST_SLACK = np.float32(4.0)  # kernels.hip kCastSlack
+CAST_SLACK = np.float32(4.0)  # casts_dev.h kCastSlack
 
 
 def guard_path_clear(q, px, py, qx, qy):
@@ -157,7 +157,7 @@ def k_move_origins(n, rng, worlds=8, steps=120):
 
 
 def test_bounded_sphere_casts_equal_full_casts_where_guard_is_clear():
-    """castNearD (kernels.hip) returns the bounded cast's hit when the path
+    """castNearD (casts_dev.h) returns the bounded cast's hit when the path
     guard is clear: its (t, normal) must equal the full cast's whenever
     either is nearer than the bound, and both must read "no hit" otherwise.
     Horizontal casts with the bounds k_move uses (forward: move_dist + buffer

@@ -46,15 +46,29 @@ KSIM_SKIP = [("fireD(", 1), ("respawnSerialD(", 2), ("zoneMatchInfoD(", 8), ("go
              ("exploreVisitedD(", 1024)]
 
 
+KSIM_FILE = "kernels.hip"  # where k_sim's body (simBody) is
+KSIM_HEAD = "void simBody(const DevState &S, const SceneDev &sc, char *img)\n{"
+
+
+def _replace(s, old, new, what):
+    if old not in s:
+        raise ValueError(f"ksim_hooks: {what} not found: {old!r}")
+    return s.replace(old, new)
+
+
 def ksim_hooks(path):
+    """Patches k_sim's hooks into the lab copy `path` of KSIM_FILE; raises
+    when an anchor is gone, so a moved body cannot leave k_sim unhooked."""
     s = open(path).read()
-    s = s.replace("constexpr int kSimBlock = 128;",
-                  "#ifndef MPENV_SIM_BLOCK\n#define MPENV_SIM_BLOCK 128\n#endif\nconstexpr int kSimBlock = MPENV_SIM_BLOCK;")
-    s = s.replace("#define MP_SIM_ATTR __attribute__((amdgpu_waves_per_eu(4)))",
-                  "#ifndef MPENV_SIM_WPE\n#define MPENV_SIM_WPE 4\n#endif\n"
-                  "#define MP_SIM_ATTR __attribute__((amdgpu_waves_per_eu(MPENV_SIM_WPE)))")
-    head = "k_sim(DevState S, SceneDev sc)\n{"
-    a = s.index(head) + len(head) - 1
+    s = _replace(s, "constexpr int kSimBlock = 128;",
+                 "#ifndef MPENV_SIM_BLOCK\n#define MPENV_SIM_BLOCK 128\n#endif\nconstexpr int kSimBlock = MPENV_SIM_BLOCK;",
+                 "block-size constant")
+    s = _replace(s, "#define MP_SIM_ATTR __attribute__((amdgpu_waves_per_eu(4)))",
+                 "#ifndef MPENV_SIM_WPE\n#define MPENV_SIM_WPE 4\n#endif\n"
+                 "#define MP_SIM_ATTR __attribute__((amdgpu_waves_per_eu(MPENV_SIM_WPE)))", "waves-per-SIMD constant")
+    if KSIM_HEAD not in s:
+        raise ValueError(f"ksim_hooks: body head not found: {KSIM_HEAD!r}")
+    a = s.index(KSIM_HEAD) + len(KSIM_HEAD) - 1
     d, k = 0, a
     while True:
         d += {"{": 1, "}": -1}.get(s[k], 0)
@@ -62,9 +76,9 @@ def ksim_hooks(path):
             break
         k += 1
     body = s[a + 1:k]
-    body = body.replace("__syncthreads();", "__syncthreads(); MP_PT();")
+    body = _replace(body, "__syncthreads();", "__syncthreads(); MP_PT();", "block barrier in k_sim's body")
     for name, bit in KSIM_SKIP:
-        body = body.replace(name, f"(MPENV_LAB_SIM_SKIP & {bit}) ? (void)0 : (void){name}")
+        body = _replace(body, name, f"(MPENV_LAB_SIM_SKIP & {bit}) ? (void)0 : (void){name}", "phase call")
     prelude = """
 #ifndef MPENV_LAB_SIM_SKIP
 #define MPENV_LAB_SIM_SKIP 0
@@ -119,22 +133,8 @@ def build(name, args):
         open(fp, "w").write(text.replace(old, new))
     if any(d.startswith(("-DMPENV_LAB_PHASE_T", "-DMPENV_LAB_SIM_SKIP", "-DMPENV_SIM_WPE", "-DMPENV_SIM_BLOCK"))
            for d in defines):
-        ksim_hooks(os.path.join(src_dir, "kernels.hip"))
-    common = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", f"-I{src_dir}",
-              f"-I{B.INCLUDE}"] + list(defines)
-    objs = []
-    for src in B.LIB_SOURCES:
-        s = os.path.join(src_dir, src)
-        o = os.path.join(out, src + ".o")
-        if src.endswith(".hip"):
-            cmd = [B.HIPCC, "-x", "hip", f"--offload-arch={B.ARCH}", "-c", s, "-o", o] + common
-        else:
-            cmd = [B.HIPCC, "-x", "c++", "-c", s, "-o", o] + common + ["-D__HIP_PLATFORM_AMD__",
-                                                                      "-I/opt/rocm/include"]
-        subprocess.run(cmd, check=True)
-        objs.append(o)
-    subprocess.run([B.HIPCC, "-shared", "-fPIC", f"--offload-arch={B.ARCH}", "-o",
-                    os.path.join(out, "libmpenv.so")] + objs, check=True)
+        ksim_hooks(os.path.join(src_dir, KSIM_FILE))
+    B.compile_and_link(src_dir, out, os.path.join(out, "libmpenv.so"), extra=defines)
     json.dump({"defines": defines, "patches": [os.path.relpath(p, ROOT) for p in patches], "subs": subs},
               open(os.path.join(out, "variant.json"), "w"))
     print("built", name, defines)

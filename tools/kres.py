@@ -1,16 +1,26 @@
 """Per-kernel resource usage (VGPRs, SGPRs, spills, scratch, occupancy, LDS)
-of csrc/kernels.hip from the compiler's kernel-resource-usage remarks.
+of every device translation unit of libmpenv.so (build_native.LIB_SOURCES),
+from the compiler's kernel-resource-usage remarks.
     python tools/kres.py [extra hipcc flags...]"""
+import os
 import re
 import subprocess
 import sys
+import tempfile
 
-ROOT = __file__.rsplit("/tools/", 1)[0]
-CSRC = ROOT + "/madrona-mp-env_amd/csrc"
-cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "--cuda-device-only", "-c",
-       CSRC + "/kernels.hip", "-o", "/tmp/kres.o", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-       "-I" + CSRC, "-I" + ROOT + "/include", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "madrona-mp-env_amd"))
+import build_native as B  # noqa: E402
+
+out = ""
+with tempfile.TemporaryDirectory() as tmp:
+    for src in B.LIB_SOURCES:
+        if not src.endswith(".hip"):
+            continue
+        cmd = B.compile_cmd(os.path.join(B.CSRC, src), os.path.join(tmp, "kres.o"), B.CSRC,
+                            extra=["-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:],
+                            mode=("--cuda-device-only", "-c"))
+        out += subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
 for line in out.splitlines():
