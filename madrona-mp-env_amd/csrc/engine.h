@@ -363,8 +363,8 @@ struct SceneDev {
 // instantiations take this as one more.
 enum : int32_t { kResidencyLds = 0, kResidencyGlobal = 1 };
 struct SceneImages {
-    char *sphere; // bvhLdsBytesSphere bytes; begins with stageBVH's image
-    char *oct;    // bvhLdsBytesOct bytes
+    char *sphere; // geom_dev.h SphereImage (begins with its CollisionImage, which stageBVH views)
+    char *oct;    // geom_dev.h OctImage
     int32_t residency;
 };
 
@@ -373,9 +373,10 @@ struct SceneImages {
 enum KernelId { kKMove = 0, kKSim = 1, kKVis = 2, kKObs = 3, kKLidar = 4, kNumTimedKernels = 5 };
 
 const char *kernelName(int k);
+// The images' total bytes (layouts: geom_dev.h CollisionImage, SphereImage, OctImage)
 size_t bvhLdsBytes(const SceneDev &sc);
-size_t bvhLdsBytesSphere(const SceneDev &sc); // + triPre (sphere-casting kernels)
-size_t bvhLdsBytesOct(const SceneDev &sc);    // octant node images + vertices (k_lidar)
+size_t bvhLdsBytesSphere(const SceneDev &sc); // sphere-casting kernels
+size_t bvhLdsBytesOct(const SceneDev &sc);    // k_lidar
 // The dynamic LDS each step kernel asks for under a residency (only the
 // scene's counts are read, so a SceneDev without device pointers will do).
 // k_vis's also depends on the team size; T = 0: the largest over all of them.

@@ -147,9 +147,66 @@ __device__ __forceinline__ uint32_t bsPop2(WideStack &s, uint32_t &, uint32_t &m
 using LBVHL = LBVHT<3, true, ByteStack>;
 using LBVHG = LBVHT<1, false, WideStack>;
 
-// Stage nodes + vertices into dynamic LDS (all threads participate).
-// LDS image: nodes verbatim (64 B each), then every triangle vertex padded
-// to a float4 so a triangle is three ds_read_b128.
+// The byte layout of the three BVH images from the scene's counts: the offset
+// of every section after the nodes, which begin an image, and the total.  The
+// staging functions below write and view an image by these; the host sizes the
+// LDS request, the global allocation and the scene's admission by the totals
+// (bvhLdsBytes*, engine.h).
+// The collision image: nodes verbatim (64 B each), then every triangle vertex
+// padded to a float4 so a triangle is three ds_read_b128.
+// (Both widths the code had: the vertices' offset counts uint4 slots in int, as
+// the copy loop does, and widens last; the total widens first.)
+struct CollisionImage {
+    int numNodes, numVerts;
+    __host__ __device__ constexpr size_t verts() const { return (size_t)(numNodes * 4) * 16; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)numNodes * 64 + (size_t)numVerts * 16; }
+};
+
+// The sphere image: the collision image (its base), then the per-triangle
+// sphere-cast constants (SceneDev::triPre, two float4 per triangle), then the
+// sphere-cast node image (kSNodeFloats per node, filled by stageBVHSphere).
+struct SphereImage : CollisionImage {
+    __host__ __device__ constexpr size_t pre() const { return CollisionImage::bytes(); }
+    __host__ __device__ constexpr size_t snodes() const { return pre() + (size_t)(numVerts / 3) * 32; }
+    __host__ __device__ constexpr size_t bytes() const { return snodes() + (size_t)numNodes * kSNodeFloats * 4; }
+};
+
+// k_lidar's image: the 8 octant node images of the lidar tree (scene.h
+// octantNodeImages, 8 x numLidarNodes nodes) then its vertices as float4
+// (three rotated copies).
+// The traversal of a ray reads image (d.x < 0) | (d.y < 0) << 1 | (d.z < 0) << 2.  Each node takes
+// kOctNodeQ = 4 16-B slots (packed 64-B nodes; a fifth pad slot, which moves
+// nodes k != k' (mod 16) to different LDS bank groups, measured no faster in
+// round 2).  The vertices follow three times, copy r as (v[r+1], v[r+2],
+// v[r]) (mod 3), for rayTriRot (one (x, y, z) copy with per-component
+// gathers: k_lidar 0.730 -> 0.744 ms, round 3).
+constexpr int kOctNodeQ = 4;
+struct OctImage {
+    int numLidarNodes, numLidarVerts;
+    __host__ __device__ constexpr size_t verts() const { return (size_t)(numLidarNodes * kOctNodeQ * 8) * 16; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)numLidarNodes * 16 * kOctNodeQ * 8 + (size_t)numLidarVerts * 16 * 3; }
+};
+
+constexpr bool imagesSound(int n, int v) // (61 and 756: simple_map; 1 and 4: odd counts, a partial triangle)
+{
+    const CollisionImage c { n, v };
+    const SphereImage s { c };
+    const OctImage o { n, v };
+    return (c.verts() | s.pre() | s.snodes() | s.bytes() | o.verts() | o.bytes()) % 16 == 0 &&
+           c.bytes() == c.verts() + (size_t)v * 16 && o.bytes() == o.verts() + (size_t)v * 48 &&
+           s.verts() == c.verts() && s.pre() == c.bytes();
+}
+static_assert(imagesSound(61, 756) && imagesSound(1, 4), "16-B sections, each ending where the next begins; sphere = collision + 2");
+static_assert(SphereImage { { 61, 756 } }.bytes() == 31872, "simple_map's sphere image (tests/test_scene_residency.py)");
+
+// The view of an image at `smem` whose vertices begin `verts` bytes in (no pre, snodes or stats).
+template <class LBVH>
+__device__ __forceinline__ LBVH bvhView(char *smem, size_t verts, int32_t rotStride)
+{
+    return { (const MP_LDS BVHNode *)(smem), (const MP_LDS float *)(smem + verts), nullptr, nullptr, nullptr, rotStride };
+}
+
+// Stage the collision image into dynamic LDS (all threads participate).
 // The collision tree: every query but the lidar's walks it (k_vis walked
 // the lidar tree in round 6 and is back: a sight answer can depend on the
 // tree, DESIGN.md section 2 definition 4).
@@ -159,38 +216,30 @@ using LBVHG = LBVHT<1, false, WideStack>;
 template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVH(char *smem, const SceneDev &sc)
 {
-    const int numNodes = sc.numNodes;
+    const CollisionImage im { sc.numNodes, sc.numVerts };
     const int numVerts = sc.numVerts;
-    const int node_q = numNodes * 4; // uint4 per node
+    const int node_q = sc.numNodes * 4; // uint4 per node
     const uint4 *src_n = reinterpret_cast<const uint4 *>(sc.nodes);
     uint4 *dst_n = reinterpret_cast<uint4 *>(smem);
     if constexpr (kWrite)
         for (int k = threadIdx.x; k < node_q; k += blockDim.x) dst_n[k] = src_n[k];
     const float *src_v = sc.verts;
-    float4 *dst_v = reinterpret_cast<float4 *>(smem + (size_t)node_q * 16);
+    float4 *dst_v = reinterpret_cast<float4 *>(smem + im.verts());
     if constexpr (kWrite)
         for (int k = threadIdx.x; k < numVerts; k += blockDim.x)
             dst_v[k] = make_float4(src_v[3 * k], src_v[3 * k + 1], src_v[3 * k + 2], 0.f);
     __syncthreads();
-    LBVH b;
-    b.nodes = (const MP_LDS BVHNode *)(smem);
-    b.verts = (const MP_LDS float *)(smem + (size_t)node_q * 16);
-    b.pre = nullptr;
-    b.snodes = nullptr;
-    b.stats = nullptr;
-    b.rotStride = 0;
-    return b;
+    return bvhView<LBVH>(smem, im.verts(), 0);
 }
 
-// stageBVH plus the per-triangle sphere-cast constants (SceneDev::triPre,
-// two float4 per triangle) after the vertices.
+// stageBVH plus the sphere image's two sections after the vertices.
 template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
 {
-    const size_t pre_off = (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16;
+    const SphereImage im { { sc.numNodes, sc.numVerts } };
     const int pre_q = (sc.numVerts / 3) * 2;
     const float4 *src_p = reinterpret_cast<const float4 *>(sc.triPre);
-    float4 *dst_p = reinterpret_cast<float4 *>(smem + pre_off);
+    float4 *dst_p = reinterpret_cast<float4 *>(smem + im.pre());
     if constexpr (kWrite)
         for (int k = threadIdx.x; k < pre_q; k += blockDim.x) dst_p[k] = src_p[k];
     // Sphere-cast node image (kSNodeFloats per node): per axis a, the
@@ -200,8 +249,7 @@ __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
     // sphereCastNodeCheck evaluates per child (mesh_bvh.inl:817-855) -- then
     // the children and triangle counts.  Built for radius kSphereR (every
     // k_move cast uses the agent radius).
-    const size_t sn_off = pre_off + (size_t)(sc.numVerts / 3) * 32;
-    float *sn = reinterpret_cast<float *>(smem + sn_off);
+    float *sn = reinterpret_cast<float *>(smem + im.snodes());
     for (int k = threadIdx.x; kWrite && k < sc.numNodes * 4; k += blockDim.x) {
         const int n = k >> 2, i = k & 3;
         const BVHNode &nd = sc.nodes[n];
@@ -231,47 +279,30 @@ __device__ __forceinline__ LBVH stageBVHSphere(char *smem, const SceneDev &sc)
         o[28 + i] = __uint_as_float((uint32_t)cnt);
     }
     LBVH b = stageBVH<LBVH, kWrite>(smem, sc); // ends with __syncthreads
-    b.pre = (const MP_LDS float *)(smem + pre_off);
-    b.snodes = (const MP_LDS float *)(smem + sn_off);
+    b.pre = (const MP_LDS float *)(smem + im.pre());
+    b.snodes = (const MP_LDS float *)(smem + im.snodes());
     return b;
 }
 
-// k_lidar's LDS image: the 8 octant node images of the lidar tree (scene.h
-// octantNodeImages, 8 x numLidarNodes nodes) then its vertices as float4
-// (three rotated copies).
-// The traversal of a ray reads image (d.x < 0) | (d.y < 0) << 1 | (d.z < 0) << 2.  Each node takes
-// kOctNodeQ = 4 16-B slots (packed 64-B nodes; a fifth pad slot, which moves
-// nodes k != k' (mod 16) to different LDS bank groups, measured no faster in
-// round 2).  The vertices follow three times, copy r as (v[r+1], v[r+2],
-// v[r]) (mod 3), for rayTriRot (one (x, y, z) copy with per-component
-// gathers: k_lidar 0.730 -> 0.744 ms, round 3).
-constexpr int kOctNodeQ = 4;
-
+// Stage k_lidar's image (OctImage); kWrite as in stageBVH.
 template <class LBVH, bool kWrite = LBVH::kStaged>
 __device__ __forceinline__ LBVH stageBVHOct(char *smem, const SceneDev &sc)
 {
-    const int node_q = sc.numLidarNodes * kOctNodeQ * 8;
+    const OctImage im { sc.numLidarNodes, sc.numLidarVerts };
     const uint4 *src_n = reinterpret_cast<const uint4 *>(sc.octNodes);
     uint4 *dst_n = reinterpret_cast<uint4 *>(smem);
     if constexpr (kWrite)
         for (int k = threadIdx.x; k < sc.numLidarNodes * 4 * 8; k += blockDim.x)
             dst_n[(k >> 2) * kOctNodeQ + (k & 3)] = src_n[k];
     const float *src_v = sc.lidarVerts;
-    float4 *dst_v = reinterpret_cast<float4 *>(smem + (size_t)node_q * 16);
+    float4 *dst_v = reinterpret_cast<float4 *>(smem + im.verts());
     for (int k = threadIdx.x; kWrite && k < sc.numLidarVerts * 3; k += blockDim.x) {
         const int r = k / sc.numLidarVerts, v = k - r * sc.numLidarVerts;
         const int r1 = r == 2 ? 0 : r + 1, r2 = r1 == 2 ? 0 : r1 + 1;
         dst_v[k] = make_float4(src_v[3 * v + r1], src_v[3 * v + r2], src_v[3 * v + r], 0.f);
     }
     __syncthreads();
-    LBVH b;
-    b.nodes = (const MP_LDS BVHNode *)(smem);
-    b.verts = (const MP_LDS float *)(smem + (size_t)node_q * 16);
-    b.pre = nullptr;
-    b.snodes = nullptr;
-    b.stats = nullptr;
-    b.rotStride = sc.numLidarVerts;
-    return b;
+    return bvhView<LBVH>(smem, im.verts(), sc.numLidarVerts);
 }
 
 // sign bits: -0 counts as negative, as in the slab test's copysign'd inverse

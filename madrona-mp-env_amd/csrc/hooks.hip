@@ -4,6 +4,22 @@
 
 namespace mpenv {
 
+// Which image a hook's kernel walks (the geometry-query hook: the image of the
+// kernel each mode stands in for), and the dynamic LDS it asks for.
+enum class HookImage { Collision, Sphere, Oct };
+
+constexpr HookImage geomImage(int mode)
+{
+    return mode == MPENV_GEOM_LIDAR_RAY ? HookImage::Oct
+           : mode == MPENV_GEOM_WORLD_RAY || mode == MPENV_GEOM_SIGHT ? HookImage::Collision : HookImage::Sphere;
+}
+
+static size_t hookLdsBytes(const SceneDev &sc, int32_t residency, HookImage image)
+{
+    if (residency == kResidencyGlobal) return 0;
+    return image == HookImage::Oct ? bvhLdsBytesOct(sc) : image == HookImage::Sphere ? bvhLdsBytesSphere(sc) : bvhLdsBytes(sc);
+}
+
 // Debug/test hook: closest-hit BVH queries for caller rays (mode 0 = the
 // traversal inlined into the step kernels, 1 = its out-of-line copy).
 template <class LBVH>
@@ -45,13 +61,8 @@ int launchTraceRays(const SceneDev &sc, const SceneImages &img, const float *o, 
                     float *t, int32_t *hit, void *stream)
 {
     if (n <= 0) return 0;
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_trace_rays_g, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, sc,
-                           o, d, n, mode, t, hit, img);
-    else
-        hipLaunchKernelGGL(k_trace_rays, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), bvhLdsBytes(sc),
-                           (hipStream_t)stream, sc, o, d, n, mode, t, hit);
-    return check(hipGetLastError());
+    return launchByResidency(img, k_trace_rays, k_trace_rays_g, dim3((n + kBlock - 1) / kBlock), dim3(kBlock),
+                             hookLdsBytes(sc, img.residency, HookImage::Collision), stream, sc, o, d, n, mode, t, hit);
 }
 
 // Test hook (mpenv_debug_geom_queries, include/mpenv.h): one geometry query
@@ -67,9 +78,8 @@ __device__ __forceinline__ void geomQueriesBody(const SceneDev &sc, const mpenv_
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LBVH bvh;
-    if constexpr (kMode == MPENV_GEOM_LIDAR_RAY) bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img.oct, sc);
-    else if constexpr (kMode == MPENV_GEOM_WORLD_RAY) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
-    else if constexpr (kMode == MPENV_GEOM_SIGHT) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
+    if constexpr (geomImage(kMode) == HookImage::Oct) bvh = stageBVHOct<LBVH>(LBVH::kStaged ? smem : img.oct, sc);
+    else if constexpr (geomImage(kMode) == HookImage::Collision) bvh = stageBVH<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
     else bvh = stageBVHSphere<LBVH>(LBVH::kStaged ? smem : img.sphere, sc);
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
@@ -162,54 +172,25 @@ __global__ void __launch_bounds__(kBlock) k_geom_queries_g(SceneDev sc, mpenv_ge
     geomQueriesBody<kMode, LBVHG>(sc, q, n, img);
 }
 
+template <int kMode>
+static int launchGeomMode(const SceneDev &sc, const SceneImages &img, int n, const mpenv_geom_queries &q, void *stream)
+{
+    return launchByResidency(img, k_geom_queries<kMode>, k_geom_queries_g<kMode>, dim3((n + kBlock - 1) / kBlock),
+                             dim3(kBlock), hookLdsBytes(sc, img.residency, geomImage(kMode)), stream, sc, q, n);
+}
+
 int launchGeomQueries(const SceneDev &sc, const SceneImages &img, int mode, int n, const mpenv_geom_queries &q,
                       void *stream)
 {
     if (n <= 0) return 0;
-    const dim3 grid((n + kBlock - 1) / kBlock), block(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (img.residency == kResidencyGlobal) {
-        switch (mode) {
-        case MPENV_GEOM_LIDAR_RAY:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_LIDAR_RAY>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_WORLD_RAY:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_WORLD_RAY>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_SIGHT:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_SIGHT>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_CASTS:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_CASTS>, grid, block, 0, st, sc, q, n, img);
-            break;
-        case MPENV_GEOM_STUCK:
-            hipLaunchKernelGGL(k_geom_queries_g<MPENV_GEOM_STUCK>, grid, block, 0, st, sc, q, n, img);
-            break;
-        default:
-            return -1;
-        }
-        return check(hipGetLastError());
-    }
     switch (mode) {
-    case MPENV_GEOM_LIDAR_RAY:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_LIDAR_RAY>, grid, block, bvhLdsBytesOct(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_WORLD_RAY:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_WORLD_RAY>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_SIGHT:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_SIGHT>, grid, block, bvhLdsBytes(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_CASTS:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_CASTS>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
-        break;
-    case MPENV_GEOM_STUCK:
-        hipLaunchKernelGGL(k_geom_queries<MPENV_GEOM_STUCK>, grid, block, bvhLdsBytesSphere(sc), st, sc, q, n);
-        break;
-    default:
-        return -1;
+    case MPENV_GEOM_LIDAR_RAY: return launchGeomMode<MPENV_GEOM_LIDAR_RAY>(sc, img, n, q, stream);
+    case MPENV_GEOM_WORLD_RAY: return launchGeomMode<MPENV_GEOM_WORLD_RAY>(sc, img, n, q, stream);
+    case MPENV_GEOM_SIGHT: return launchGeomMode<MPENV_GEOM_SIGHT>(sc, img, n, q, stream);
+    case MPENV_GEOM_CASTS: return launchGeomMode<MPENV_GEOM_CASTS>(sc, img, n, q, stream);
+    case MPENV_GEOM_STUCK: return launchGeomMode<MPENV_GEOM_STUCK>(sc, img, n, q, stream);
+    default: return -1;
     }
-    return check(hipGetLastError());
 }
 
 // Debug gather of internal state into the MPENV_EXPORT_DEBUG_* layouts.

@@ -2007,7 +2007,7 @@ static_assert(kSimReuseBytes == kSimKeyBytes + kSimRecBytes, "the keys and the r
 template <bool kStaged>
 __host__ __device__ size_t simSpawnOffset(const SceneDev &sc)
 {
-    const size_t bvh = kStaged ? (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16 : 0;
+    const size_t bvh = kStaged ? CollisionImage { sc.numNodes, sc.numVerts }.bytes() : 0;
     return ((bvh > kSimReuseBytes ? bvh : kSimReuseBytes) + 15) & ~(size_t)15;
 }
 
@@ -2433,7 +2433,9 @@ const char *kernelName(int k)
     return (k >= 0 && k < kNumTimedKernels) ? names[k] : "?";
 }
 
-size_t bvhLdsBytes(const SceneDev &sc) { return (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16; }
+size_t bvhLdsBytes(const SceneDev &sc) { return CollisionImage { sc.numNodes, sc.numVerts }.bytes(); }
+size_t bvhLdsBytesSphere(const SceneDev &sc) { return SphereImage { { sc.numNodes, sc.numVerts } }.bytes(); }
+size_t bvhLdsBytesOct(const SceneDev &sc) { return OctImage { sc.numLidarNodes, sc.numLidarVerts }.bytes(); }
 
 // The step kernels' dynamic LDS under a residency: global-resident, only
 // what a kernel keeps beside the image is left.
@@ -2449,16 +2451,6 @@ int buildSceneImages(const SceneDev &sc, const SceneImages &img, void *stream)
     int rc = check(hipGetLastError());
     if (!rc) rc = check(hipStreamSynchronize((hipStream_t)stream));
     return rc;
-}
-
-size_t bvhLdsBytesSphere(const SceneDev &sc)
-{
-    return bvhLdsBytes(sc) + (size_t)(sc.numVerts / 3) * 32 + (size_t)sc.numNodes * kSNodeFloats * 4;
-}
-
-size_t bvhLdsBytesOct(const SceneDev &sc)
-{
-    return (size_t)sc.numLidarNodes * 16 * kOctNodeQ * 8 + (size_t)sc.numLidarVerts * 16 * 3;
 }
 
 int launchConstruct(const DevState &s, const SceneDev &sc, const int32_t tc[3], void *stream)
@@ -2482,13 +2474,8 @@ int launchSimStep(const DevState &s, const SceneDev &sc, const SceneImages &img,
 {
     const int wpb = kSimBlock / s.N;
     const int blocks = (s.W + wpb - 1) / wpb;
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_sim_g, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, kResidencyGlobal),
-                           (hipStream_t)stream, s, sc, img);
-    else
-        hipLaunchKernelGGL(k_sim, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, kResidencyLds), (hipStream_t)stream,
-                           s, sc);
-    return check(hipGetLastError());
+    return launchByResidency(img, k_sim, k_sim_g, dim3(blocks), dim3(kSimBlock), simLdsBytes(sc, img.residency),
+                             stream, s, sc);
 }
 
 int computeSceneFrames(SceneTables *d_tab, void *stream)

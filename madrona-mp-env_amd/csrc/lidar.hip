@@ -388,13 +388,8 @@ int launchLidar(const DevState &s, const SceneDev &sc, const SceneImages &img, i
     const int64_t tasks = lidarTasks(s.A);
     const int64_t per_block = (int64_t)kLidarWaves * iters;
     const int blocks = (int)((tasks + per_block - 1) / per_block);
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_lidar_g, dim3(blocks), dim3(kLidarBlock), lidarLdsBytes(sc, kResidencyGlobal),
-                           (hipStream_t)stream, s, sc, iters, img);
-    else
-        hipLaunchKernelGGL(k_lidar, dim3(blocks), dim3(kLidarBlock), lidarLdsBytes(sc, kResidencyLds),
-                           (hipStream_t)stream, s, sc, iters);
-    return check(hipGetLastError());
+    return launchByResidency(img, k_lidar, k_lidar_g, dim3(blocks), dim3(kLidarBlock),
+                             lidarLdsBytes(sc, img.residency), stream, s, sc, iters);
 }
 
 } // namespace mpenv

@@ -390,13 +390,8 @@ int launchMove(const DevState &s, const SceneDev &sc, const SceneImages &img, vo
     const int64_t waves = (s.A + apw - 1) / apw;
     const int bs = waves < 64 * 4 ? 64 : kBlock;
     const int64_t threads = waves * 64;
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_move_g, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs),
-                           moveLdsBytes(sc, kResidencyGlobal), (hipStream_t)stream, s, sc, apw, img);
-    else
-        hipLaunchKernelGGL(k_move, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs),
-                           moveLdsBytes(sc, kResidencyLds), (hipStream_t)stream, s, sc, apw);
-    return check(hipGetLastError());
+    return launchByResidency(img, k_move, k_move_g, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs),
+                             moveLdsBytes(sc, img.residency), stream, s, sc, apw);
 }
 
 } // namespace mpenv

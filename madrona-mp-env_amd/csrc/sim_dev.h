@@ -1,6 +1,6 @@
 // sim_dev.h — what the kernel files of the step share (kernels.hip, move.hip,
 // hooks.hip): the reference's constants, the SoA accessors, the block size
-// and block order, and the launchers' error check.
+// and block order, and the launchers' error check and launch by residency.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -147,5 +147,18 @@ __device__ __forceinline__ int exploreBitD(int cx, int cy) { return (cy & 7) * 8
 __device__ __forceinline__ int exploreTileD(int cx, int cy) { return (cy >> 3) * kExploreTilesX + (cx >> 3); }
 
 static int check(hipError_t e) { return e == hipSuccess ? 0 : -1; }
+
+// Launches a BVH kernel by the images' residency: `lds`, which stages them into `ldsBytes` (its
+// *LdsBytes(sc, img.residency)) of dynamic LDS, or `glb`, its `_g` twin with the images as one more parameter.
+template <class... P>
+static int launchByResidency(const SceneImages &img, void (*lds)(P...), void (*glb)(P..., SceneImages), dim3 grid,
+                             dim3 block, size_t ldsBytes, void *stream, const P &...args)
+{
+    if (img.residency == kResidencyGlobal)
+        hipLaunchKernelGGL(glb, grid, block, ldsBytes, (hipStream_t)stream, args..., img);
+    else
+        hipLaunchKernelGGL(lds, grid, block, ldsBytes, (hipStream_t)stream, args...);
+    return check(hipGetLastError());
+}
 
 } // namespace mpenv

@@ -44,7 +44,7 @@ __device__ __forceinline__ void visBody(const DevState &S, const SceneDev &sc, c
     const int64_t wave = ((int64_t)xcdBlockId() * blockDim.x + threadIdx.x) >> 6;
     const int64_t agent0 = (((int64_t)xcdBlockId() * blockDim.x) >> 6) * apw; // first agent of the block
     const int nsMax = visStageAgents(T, N);
-    float *st = (float *)(smem + (LBVH::kStaged ? (size_t)sc.numNodes * 64 + (size_t)sc.numVerts * 16 : 0));
+    float *st = (float *)(smem + (LBVH::kStaged ? CollisionImage { sc.numNodes, sc.numVerts }.bytes() : 0));
     const int64_t s0 = (agent0 / N) * N;
     {
         const int64_t a_hi = min(S.A, agent0 + (int64_t)(kBlock / 64) * apw);
@@ -237,13 +237,8 @@ int launchVisibility(const DevState &s, const SceneDev &sc, const SceneImages &i
 {
     const int64_t waves = (s.A + (64 / s.T) - 1) / (64 / s.T);
     const int blocks = (int)((waves * 64 + kBlock - 1) / kBlock);
-    if (img.residency == kResidencyGlobal)
-        hipLaunchKernelGGL(k_vis_g, dim3(blocks), dim3(kBlock), visLdsBytes(sc, kResidencyGlobal, s.T),
-                           (hipStream_t)stream, s, sc, img);
-    else
-        hipLaunchKernelGGL(k_vis, dim3(blocks), dim3(kBlock), visLdsBytes(sc, kResidencyLds, s.T),
-                           (hipStream_t)stream, s, sc);
-    return check(hipGetLastError());
+    return launchByResidency(img, k_vis, k_vis_g, dim3(blocks), dim3(kBlock), visLdsBytes(sc, img.residency, s.T),
+                             stream, s, sc);
 }
 
 } // namespace mpenv

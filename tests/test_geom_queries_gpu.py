@@ -8,12 +8,14 @@ that they reach the cases they are built for).  The hook compiles the step
 kernels' device functions a second time; the step kernels' own code
 generation stays with the whole-step parity tests."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 import geom_cases as G
 import mpenv_testlib as T
+import scene_residency_testlib as R
 
 pytestmark = pytest.mark.gpu
 
@@ -208,17 +210,22 @@ def test_sphere_casts_full_bounded_and_paired_match_oracle(engine):
     assert compared > 1000
 
 
-def test_stuck_casts_dealt_over_partial_waves_match_serial_oracle(engine):
-    """stuckCastsD as applyVelocityD calls it, on waves with lanes that have
-    left, with 0 .. every active lane stuck (1, 2 and 4 dealing rounds): hd4
-    of every active lane with `need` equals the four serial casts of
-    sim.cpp:962-984; every other lane's hd4 keeps its NaN-pattern prefill."""
+@functools.lru_cache(maxsize=None)
+def _stuck_ref():
+    """G.stuck_waves() and the oracle's hd4 for every lane of it, computed once."""
     w = G.stuck_waves()
+    return w, G.stuck_oracle(w["x"], w["v"], w["low_check"])
+
+
+def _check_stuck(engine, lanes):
+    """Launches the STUCK hook on the first k lanes for every k of lanes(n),
+    the last being the whole set n: hd4 of the lanes with `need` equals the
+    oracle's bit for bit, every other lane keeps its NaN-pattern prefill."""
+    w, ref = _stuck_ref()
     n = len(w["flags"])
-    ref = G.stuck_oracle(w["x"], w["v"], w["low_check"])
     fill = (np.uint32(0x7fc0a000) + np.arange(n * 4, dtype=np.uint32)).reshape(n, 4)
     hook = Hook(engine, o=w["x"], d=w["v"], bound=w["low_check"], sel=w["flags"])
-    for k in sorted({64, 256 + 64, n}):  # one wave, a block and a wave, every wave
+    for k in lanes(n):
         r = hook.run(STUCK, k, dict(t=((n, 4), np.float32)), t_init=fill)
         got = r["t"]
         need = np.zeros(n, bool)
@@ -226,3 +233,25 @@ def test_stuck_casts_dealt_over_partial_waves_match_serial_oracle(engine):
         T.compare(got[need], ref[need], f"stuck hd4 lanes={k}")
         T.compare(got[~need].view(np.uint32), fill[~need], f"stuck untouched lanes={k}")
     assert need.sum() > 300
+
+
+def test_stuck_casts_dealt_over_partial_waves_match_serial_oracle(engine):
+    """stuckCastsD as applyVelocityD calls it, on waves with lanes that have
+    left, with 0 .. every active lane stuck (1, 2 and 4 dealing rounds): hd4
+    of every active lane with `need` equals the four serial casts of
+    sim.cpp:962-984; every other lane's hd4 keeps its NaN-pattern prefill."""
+    _check_stuck(engine, lambda n: sorted({64, 256 + 64, n}))  # one wave, a block and a wave, every wave
+
+
+def test_stuck_casts_on_the_global_images_match_serial_oracle():
+    """The same check through k_geom_queries_g<STUCK>: simple_map switched to
+    the global-resident images (no other test runs this mode of the hook
+    there), on the first wave and on every wave."""
+    import torch  # noqa: F401  (before the engine initialises HIP, as in engine())
+    e = T.Engine(1, 1)
+    try:
+        assert R.set_residency(e, R.GLOBAL) == 0, e.lib.mpenv_last_error().decode()
+        assert R.residency(e) == R.GLOBAL
+        _check_stuck(e, lambda n: [64, n])
+    finally:
+        e.close()
