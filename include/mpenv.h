@@ -305,7 +305,8 @@ static_assert(sizeof(mpenv_packed_step_snapshot) == 192, "PackedStepSnapshot lay
 #define MPENV_DTYPE_INT32 0
 #define MPENV_DTYPE_FLOAT32 1
 #define MPENV_DTYPE_UINT32 2
-/* snapshot sections only (mpenv_state_section_dtype); no export has them */
+/* snapshot sections (mpenv_state_section_dtype) and the camera's label image
+ * (mpenv_camera_tensor, UINT8) only; no export has them */
 #define MPENV_DTYPE_UINT8 3
 #define MPENV_DTYPE_UINT16 4
 #define MPENV_DTYPE_UINT64 5
@@ -693,6 +694,9 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
 /* scene residency: MPENV_SCENE_AUTO / _LDS / _GLOBAL, mpenv_set_scene_residency,
  * mpenv_scene_residency, and mpenv_scene_info with mpenv_scene_info_t */
 #include "mpenv_scene_residency.h"
+/* the egocentric depth camera: mpenv_camera_config, mpenv_camera_enable / _disable / _enabled /
+ * _render / _tensor, and mpenv_camera_layout and mpenv_camera_rays without a manager */
+#include "mpenv_camera.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

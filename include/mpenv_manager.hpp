@@ -231,6 +231,34 @@ public:
         check(mpenv_scene_residency(mgr_, &mode));
         return mode;
     }
+    // extension: the egocentric depth camera (mpenv_camera.h): per agent a [height][width] depth (f32) and
+    // label (u8) image behind every step and init while enabled; width and height multiples of 8 in [8, 128],
+    // hfovDeg in (0, 170).  enableCamera again with another size replaces the camera.
+    void enableCamera(int width, int height, float hfovDeg = 90.f)
+    {
+        const mpenv_camera_config c { width, height, hfovDeg, 0 };
+        check(mpenv_camera_enable(mgr_, &c));
+    }
+    void disableCamera() { check(mpenv_camera_disable(mgr_)); }
+    // whether a camera is enabled, and (cfg non-null) its configuration
+    bool cameraEnabled(mpenv_camera_config *cfg = nullptr) const
+    {
+        int32_t on = 0;
+        check(mpenv_camera_enabled(mgr_, cfg, &on));
+        return on != 0;
+    }
+    // the images of the current state, without a step; strm null: the manager's own stream, waited for
+    void renderCamera(void *strm = nullptr) { check(mpenv_camera_render(mgr_, strm)); }
+    // device pointers to [A][height][width] f32 / u8 and the three dims (may be null); they hold until the
+    // next enableCamera or disableCamera
+    float *cameraDepth(int64_t *dims = nullptr) const
+    {
+        return static_cast<float *>(cameraImage(MPENV_CAMERA_DEPTH, dims));
+    }
+    uint8_t *cameraLabel(int64_t *dims = nullptr) const
+    {
+        return static_cast<uint8_t *>(cameraImage(MPENV_CAMERA_LABEL, dims));
+    }
     // every agent through policyId's checkpoint
     void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
     {
@@ -361,6 +389,16 @@ private:
     static void check(int rc)
     {
         if (rc != MPENV_OK) throw std::runtime_error(std::string("mpenv: ") + mpenv_last_error());
+    }
+
+    void *cameraImage(int32_t which, int64_t *dims) const
+    {
+        void *p = nullptr;
+        int32_t dtype = 0, ndim = 0;
+        int64_t d[8] = {};
+        check(mpenv_camera_tensor(mgr_, which, &p, &dtype, &ndim, d, nullptr));
+        for (int k = 0; dims && k < ndim; k++) dims[k] = d[k];
+        return p;
     }
 
     // bindings.cpp:56-78 builds the four paths from one scene directory;

@@ -220,6 +220,10 @@ void mpenv_manager::runStep(hipStream_t st)
     if (polLoaded) launched(launchPolicyStep(S, polDev, st, kPolicyAll, polPrecision), "policy launch failed");
     preStep(st);
     launchStep(st);
+    // the camera's images of the state the step left (after the world
+    // groups' join, over the whole batch); behind the captured graph, which
+    // enabling or disabling a camera leaves alone
+    if (camOn) renderCamera(st);
     postStep(st);
 }
 
@@ -335,6 +339,7 @@ void mpenv_manager::runInitGraph(hipStream_t st)
     launched(launchVisibility(S, sc, img, st), "k_vis launch failed");
     launched(launchObservations(S, sc, st), "k_obs launch failed");
     launched(launchLidar(S, sc, img, lidarItersOf(S), st), "k_lidar launch failed");
+    if (camOn) renderCamera(st);
 }
 
 template <typename T>

@@ -1,5 +1,5 @@
-// manager.h — what manager.cpp and manager_scene.cpp share, and nothing else
-// includes: the error channel of the C ABI, the owning HIP handle types and
+// manager.h — what manager.cpp, manager_scene.cpp and camera.cpp share, and
+// nothing else includes: the error channel of the C ABI, the owning HIP handle types and
 // struct mpenv_manager.
 #pragma once
 
@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "camera.h"
 #include "engine.h"
 #include "mpenv.h"
 #include "policy.h"
@@ -272,6 +273,15 @@ struct mpenv_manager {
     // gpuStreamStep or an init writes them again; those three calls are
     // refused meanwhile (staleExports)
     bool exportsStale = false;
+    // The egocentric camera (camera.cpp, mpenv_camera.h; DESIGN.md §2
+    // definition 18): one allocation for both images and the ray tables.
+    // While on, every step and init is followed by k_camera on its stream,
+    // outside the captured graph; no part of the state, the snapshots, the
+    // wire format or the graph's key.
+    bool camOn = false;
+    mpenv_camera_config camCfg {};
+    CameraDev cam {};
+    DevPtr camBuf;
 
     ~mpenv_manager();
 
@@ -308,6 +318,7 @@ struct mpenv_manager {
     void launchStepDirect(hipStream_t st);
     void setupGroups(int want);
     void runInitGraph(hipStream_t st);
+    void renderCamera(hipStream_t st); // camera.cpp
     bool exportDesc(int32_t id, TensorDesc &d);
     void *exportPtr(int32_t id);
     void gatherDebug(bool explore = false);

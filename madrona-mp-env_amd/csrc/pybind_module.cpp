@@ -6,6 +6,7 @@
 // return zero-copy views of engine-owned device memory; .to_torch() hands
 // them to PyTorch through DLPack (kDLROCM), like madrona::py::Tensor
 // (mgr.cpp:295-301, 655-661).
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -71,8 +72,9 @@ struct PyTensor {
         mt->dl_tensor.data = ptr;
         mt->dl_tensor.device = { gpu >= 0 ? kDLROCM : kDLCPU, gpu >= 0 ? gpu : 0 };
         mt->dl_tensor.ndim = (int32_t)dims.size();
-        uint8_t code = dtype == MPENV_DTYPE_FLOAT32 ? 2 : (dtype == MPENV_DTYPE_UINT32 ? 1 : 0);
-        mt->dl_tensor.dtype = { code, 32, 1 };
+        // kDLInt 0, kDLUInt 1, kDLFloat 2; the camera's label image is the one 8-bit tensor
+        uint8_t code = dtype == MPENV_DTYPE_FLOAT32 ? 2 : (dtype == MPENV_DTYPE_UINT32 || dtype == MPENV_DTYPE_UINT8 ? 1 : 0);
+        mt->dl_tensor.dtype = { code, (uint8_t)(dtype == MPENV_DTYPE_UINT8 ? 8 : 32), 1 };
         mt->dl_tensor.shape = ctx->shape.data();
         mt->dl_tensor.strides = nullptr;
         mt->dl_tensor.byte_offset = 0;
@@ -100,6 +102,18 @@ struct PySimManager {
         int32_t ndim = 0;
         int64_t dims[8];
         check(mpenv_export_tensor(h->mgr, id, &t.ptr, &t.dtype, &ndim, dims, &t.gpu));
+        t.dims.assign(dims, dims + ndim);
+        return t;
+    }
+
+    // the camera's depth (MPENV_CAMERA_DEPTH) or label image (mpenv_camera.h)
+    PyTensor cameraTensor(int32_t which) const
+    {
+        PyTensor t;
+        t.owner = h;
+        int32_t ndim = 0;
+        int64_t dims[8];
+        check(mpenv_camera_tensor(h->mgr, which, &t.ptr, &t.dtype, &ndim, dims, &t.gpu));
         t.dims.assign(dims, dims + ndim);
         return t;
     }
@@ -174,7 +188,10 @@ PYBIND11_MODULE(madrona_mp_env, m)
     py::class_<PyTensor>(m, "Tensor")
         .def_property_readonly("shape", [](const PyTensor &t) { return py::tuple(py::cast(t.dims)); })
         .def_property_readonly("dtype", [](const PyTensor &t) {
-            return t.dtype == MPENV_DTYPE_FLOAT32 ? "float32" : (t.dtype == MPENV_DTYPE_UINT32 ? "uint32" : "int32");
+            return t.dtype == MPENV_DTYPE_FLOAT32  ? "float32"
+                   : t.dtype == MPENV_DTYPE_UINT32 ? "uint32"
+                   : t.dtype == MPENV_DTYPE_UINT8  ? "uint8"
+                                                   : "int32";
         })
         .def_property_readonly("gpu_id", [](const PyTensor &t) { return t.gpu; })
         .def("data_ptr", [](const PyTensor &t) { return reinterpret_cast<uintptr_t>(t.ptr); })
@@ -371,6 +388,28 @@ PYBIND11_MODULE(madrona_mp_env, m)
             check(mpenv_scene_residency(s.h->mgr, &mode));
             return std::string(mode == MPENV_SCENE_LDS ? "lds" : "global");
         })
+        // the egocentric depth camera (mpenv_camera.h): per agent a [height][width] depth (float32) and
+        // label (uint8: 0 nothing, 1 map, 2 teammate, 3 opponent) image, rendered behind every step and
+        // init while enabled, and by render_camera() from the current state
+        .def("enable_camera", [](PySimManager &s, int32_t width, int32_t height, float hfov_deg) {
+            const mpenv_camera_config c { width, height, hfov_deg, 0 };
+            check(mpenv_camera_enable(s.h->mgr, &c));
+        }, py::arg("width"), py::arg("height"), py::arg("hfov_deg") = 90.0f)
+        .def("disable_camera", [](PySimManager &s) { check(mpenv_camera_disable(s.h->mgr)); })
+        // (width, height, hfov_deg), or None while disabled
+        .def("camera_config", [](PySimManager &s) -> py::object {
+            mpenv_camera_config c {};
+            int32_t on = 0;
+            check(mpenv_camera_enabled(s.h->mgr, &c, &on));
+            if (!on) return py::none();
+            return py::make_tuple(c.width, c.height, c.hfov_deg);
+        })
+        .def("render_camera", [](PySimManager &s, uintptr_t stream) {
+            py::gil_scoped_release nogil;
+            check(mpenv_camera_render(s.h->mgr, reinterpret_cast<void *>(stream)));
+        }, py::arg("stream") = 0)
+        .def("camera_depth", [](PySimManager &s) { return s.cameraTensor(MPENV_CAMERA_DEPTH); })
+        .def("camera_label", [](PySimManager &s) { return s.cameraTensor(MPENV_CAMERA_LABEL); })
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
         .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
         .def("graph_status", [](PySimManager &s) {
@@ -536,6 +575,34 @@ PYBIND11_MODULE(madrona_mp_env, m)
         d["reason"] = std::string(i.reason);
         return d;
     }, py::arg("path"));
+    // the camera model without a GPU (mpenv_camera.h): the two buffers' bytes for a batch, and the rays
+    // of n agents -- pos [n, 3], aim_quat [n, 4] (w, x, y, z), cur_pose [n] -> (origins [n, 3],
+    // directions [n, height, width, 3]), bit for bit what the kernel traces
+    m.def("camera_layout", [](int32_t width, int32_t height, float hfov_deg, uint32_t num_worlds, uint32_t team_size) {
+        const mpenv_camera_config c { width, height, hfov_deg, 0 };
+        int64_t depth = 0, label = 0;
+        check(mpenv_camera_layout(&c, num_worlds, team_size, &depth, &label));
+        return py::dict(py::arg("shape") = py::make_tuple((int64_t)num_worlds * 2 * team_size, height, width),
+                        py::arg("depth_bytes") = depth, py::arg("label_bytes") = label);
+    }, py::arg("width"), py::arg("height"), py::arg("hfov_deg") = 90.0f, py::arg("num_worlds") = 1,
+          py::arg("team_size") = 1);
+    m.def("camera_rays", [](int32_t width, int32_t height, float hfov_deg,
+                            py::array_t<float, py::array::c_style | py::array::forcecast> pos,
+                            py::array_t<float, py::array::c_style | py::array::forcecast> aim_quat,
+                            py::array_t<int32_t, py::array::c_style | py::array::forcecast> cur_pose) {
+        const mpenv_camera_config c { width, height, hfov_deg, 0 };
+        const py::ssize_t n = cur_pose.size();
+        if (pos.size() != 3 * n || aim_quat.size() != 4 * n)
+            throw py::value_error("camera_rays: pos must be [n, 3] and aim_quat [n, 4] for cur_pose [n]");
+        int64_t unused = 0;
+        check(mpenv_camera_layout(&c, 1, 1, &unused, nullptr)); // the configuration, before the outputs are sized by it
+        py::array_t<float> org({ n, (py::ssize_t)3 });
+        py::array_t<float> dir({ n, (py::ssize_t)height, (py::ssize_t)width, (py::ssize_t)3 });
+        check(mpenv_camera_rays(&c, (int32_t)n, pos.data(), aim_quat.data(), cur_pose.data(), org.mutable_data(),
+                                dir.mutable_data()));
+        return py::make_tuple(org, dir);
+    }, py::arg("width"), py::arg("height"), py::arg("hfov_deg"), py::arg("pos"), py::arg("aim_quat"),
+          py::arg("cur_pose"));
     m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;
