@@ -3247,6 +3247,72 @@ void refreshDebug(Oracle &o)
     }
 }
 
+// The inverse of refreshDebug: Agent and World state from the DEBUG_* buffers
+// (a test edits them through oracle_export's pointers).  The explore grid
+// and everything no debug column carries stay as they are.
+void putDebug(Oracle &o)
+{
+    const size_t A = (size_t)o.W * o.N;
+    for (size_t g = 0; g < A; g++) {
+        Agent &a = o.agents[g];
+        const float *f = &o.dbgAF[g * MPENV_DBG_AF_COUNT];
+        a.pos = v3(f[0], f[1], f[2]);
+        a.vel = v3(f[3], f[4], f[5]);
+        a.rot = quat(f[6], f[7], f[8], f[9]);
+        a.aimYaw = f[10]; a.aimPitch = f[11];
+        a.aimRot = quat(f[12], f[13], f[14], f[15]);
+        a.maxVelocity = f[16]; a.minDistToZone = f[17]; a.firedShotT = f[18]; a.totalPenalty = f[19];
+        a.startPos = v3(f[20], f[21], f[22]);
+        a.minDistToSubZone = f[23];
+        const int32_t *n = &o.dbgAI[g * MPENV_DBG_AI_COUNT];
+        a.curPose = n[0]; a.tgtPose = n[1]; a.transitionRemaining = n[2];
+        a.rng.key.a = (uint32_t)n[3]; a.rng.key.b = (uint32_t)n[4]; a.rng.ctr = (uint32_t)n[5];
+        a.landedShotOn = n[6]; a.remainingRespawnSteps = n[7]; a.remainingStepsBeforeAutoheal = n[8];
+        a.successfulKill = (n[9] & 1) != 0; a.wasKilled = (n[9] & 2) != 0; a.inZone = (n[9] & 4) != 0;
+        a.hasDiedDuringEpisode = (n[9] & 8) != 0; a.reloadedFullMag = (n[9] & 16) != 0;
+        a.inSubZone = (n[9] & 32) != 0;
+        a.wasShotCount = n[10]; a.weaponType = n[11]; a.lastBreadcrumb = (int64_t)n[12];
+        a.stepsSinceLastNewBreadcrumb = n[13];
+        for (int k = 0; k < kMaxTeamSize; k++) a.canSee[k] = ((n[14] >> k) & 1) != 0;
+        a.numNewCellsVisited = (uint32_t)n[15];
+    }
+    for (int w = 0; w < o.W; w++) {
+        World &wd = o.worlds[w];
+        const int32_t *n = &o.dbgWI[(size_t)w * MPENV_DBG_WI_COUNT];
+        wd.teamA = n[0]; wd.curStep = n[1]; wd.isFinished = n[2] != 0; wd.curZone = n[3];
+        wd.curControllingTeam = n[4]; wd.isContested = n[5] != 0; wd.isCaptured = n[6] != 0;
+        wd.earnedPoint = n[7] != 0;
+        wd.zoneStepsRemaining = n[8]; wd.stepsUntilPoint = n[9]; wd.curEpisodeIdx = (uint32_t)n[10];
+        wd.worldEpisodeCounter = (uint32_t)n[11]; wd.baseRNG.key.a = (uint32_t)n[12];
+        wd.baseRNG.key.b = (uint32_t)n[13]; wd.baseRNG.ctr = (uint32_t)n[14];
+        // the columns carry the low words
+        for (int k = 0; k < 2; k++)
+            wd.filtersActive[k] = (wd.filtersActive[k] & ~0xffffffffull) | (uint64_t)(uint32_t)n[16 + k];
+        wd.filtersLastMatchedStep[0] = n[18]; wd.filtersLastMatchedStep[1] = n[19];
+        wd.crumbOverflow = n[20];
+        const uint32_t sub = (uint32_t)n[21];
+        for (int k = 0; k < 8; k++) {
+            const uint32_t nib = (sub >> (4 * k)) & 15u;
+            wd.subCtrl[k] = (int)(nib & 3u) - 1;
+            wd.subContested[k] = (nib & 4u) != 0;
+            wd.subCaptured[k] = (nib & 8u) != 0;
+        }
+        const float *f = &o.dbgWF[(size_t)w * MPENV_DBG_WF_COUNT];
+        wd.teamRewards[0] = f[0]; wd.teamRewards[1] = f[1];
+        wd.minDistToRegions[0] = f[2]; wd.minDistToRegions[1] = f[3];
+        wd.teamStepRewards[0] = f[4]; wd.teamStepRewards[1] = f[5];
+        const int nc = std::min(std::max(n[15], 0), (int)MPENV_MAX_CRUMBS);
+        const float *c = &o.dbgCrumbs[(size_t)w * MPENV_MAX_CRUMBS * 8];
+        wd.crumbs.resize((size_t)nc);
+        for (int k = 0; k < nc; k++) {
+            const float *e = &c[k * 8];
+            Crumb &cr = wd.crumbs[k];
+            cr.pos = v3(e[0], e[1], e[2]); cr.penalty = e[3];
+            cr.team = (int)e[4]; cr.offset = (int)e[5]; cr.id = (uint32_t)e[6];
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -3505,6 +3571,8 @@ void oracle_step_worlds(void *h, int32_t w0, int32_t w1)
 }
 
 void oracle_refresh_debug(void *h) { refreshDebug(*static_cast<Oracle *>(h)); }
+
+void oracle_put_debug(void *h) { putDebug(*static_cast<Oracle *>(h)); }
 
 void oracle_set_curriculum(void *h, const void *snapshots, int32_t n)
 {

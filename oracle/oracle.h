@@ -61,6 +61,13 @@ void oracle_step(void *h);
 void oracle_step_worlds(void *h, int32_t w0, int32_t w1);
 /* Refresh MPENV_EXPORT_DEBUG_* buffers from internal state. */
 void oracle_refresh_debug(void *h);
+/* The inverse: Agent and World state from the MPENV_EXPORT_DEBUG_* buffers as
+ * the caller left them (AGENT_F32 / AGENT_I32 / WORLD_I32 / WORLD_F32 and
+ * CRUMBS, the crumb list's length from WORLD_I32[15]); DEBUG_EXPLORE is not
+ * read.  With the state-backed exports (HP, ALIVE, MAGAZINE, FWD_LIDAR,
+ * AGENT_POLICY, last-known rows), which are written in place, a test can pose
+ * any state the debug columns describe. */
+void oracle_put_debug(void *h);
 /* Record / replay / event-log modes (sim.cpp:4750-4843, 23-106): buffers
  * exported as MPENV_EXPORT_RECORD_LOG / REPLAY_LOG / EVENT_LOG /
  * PACKED_STEP_SNAPSHOT / SNAPSHOT_WRITTEN; in replay mode the caller fills

@@ -128,7 +128,7 @@ def lib_oracle():
         lib.oracle_export.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int64)]
-        for fn in ("oracle_init", "oracle_step", "oracle_refresh_debug"):
+        for fn in ("oracle_init", "oracle_step", "oracle_refresh_debug", "oracle_put_debug"):
             getattr(lib, fn).argtypes = [C.c_void_p]
         lib.oracle_step_worlds.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         lib.oracle_set_log_modes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
@@ -307,6 +307,10 @@ class Oracle:
         if name.startswith("DEBUG"):
             self.lib.oracle_refresh_debug(self.h)
         return self.view(name).copy()
+
+    def put_debug(self):
+        """Agent and world state from the DEBUG_* buffers as edited through view()."""
+        self.lib.oracle_put_debug(self.h)
 
     def navmesh(self):
         """The oracle's own (tri_verts [T,3,3], adjacency [T,3], astar [T,T])."""
