@@ -697,6 +697,9 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
 /* the egocentric depth camera: mpenv_camera_config, mpenv_camera_enable / _disable / _enabled /
  * _render / _tensor, and mpenv_camera_layout and mpenv_camera_rays without a manager */
 #include "mpenv_camera.h"
+/* map sets, one batch over several maps: mpenv_map_range, mpenv_map_desc, mpenv_create_maps,
+ * mpenv_num_maps, mpenv_map_info, mpenv_map_of_world, mpenv_maps_plan and MPENV_STATE_ERR_CROSS_MAP */
+#include "mpenv_maps.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

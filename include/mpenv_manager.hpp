@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mpenv.h"
@@ -131,13 +132,23 @@ public:
         const char *curriculumDataPath = nullptr;
         const char *policyWeightsPath = nullptr;
         uint32_t worldIDOffset = 0; // extension: first global world id (sharding)
+        // extension: a map set (mpenv_maps.h): scene directory and number of worlds per range, the counts
+        // summing to numWorlds; empty: `map`, as in mgr.hpp.  With maps, `map` is not read.
+        std::vector<std::pair<std::string, uint32_t>> maps;
+    };
+    // one range of a map set, as the engine holds it (mapInfo)
+    struct MapInfo {
+        std::string scenePath;
+        int32_t firstWorld, numWorlds;
+        int32_t scene;     // index of the loaded scene; equal paths share one
+        int32_t residency; // MPENV_SCENE_LDS or MPENV_SCENE_GLOBAL, in use
     };
 
     // mgr.hpp:54-56; viz must be null (there is no viewer)
     explicit Manager(const Config &cfg, VizState *viz = nullptr)
     {
         if (viz != nullptr) throw std::runtime_error("mpenv: the viewer (VizState) is not part of this engine");
-        const std::string dir = sceneDir(cfg.map);
+        const std::string dir = cfg.maps.empty() ? sceneDir(cfg.map) : std::string();
         if (cfg.map.mapOffset.x != 0.f || cfg.map.mapOffset.y != 0.f || cfg.map.mapOffset.z != 0.f ||
             cfg.map.mapRotation != 0.f)
             throw std::runtime_error("mpenv: mapOffset/mapRotation must be zero (bindings.cpp:79-80)");
@@ -153,14 +164,20 @@ public:
         c.team_size = cfg.teamSize;
         c.num_pbt_policies = cfg.numPBTPolicies;
         c.policy_history_size = cfg.policyHistorySize;
-        c.scene_path = dir.c_str();
+        c.scene_path = cfg.maps.empty() ? dir.c_str() : nullptr;
         c.train_flank = cfg.trainFlank ? 1 : 0;
         c.replay_log_path = cfg.replayLogPath;
         c.record_log_path = cfg.recordLogPath;
         c.event_log_path = cfg.eventLogPath;
         c.curriculum_data_path = cfg.curriculumDataPath;
         c.world_id_offset = cfg.worldIDOffset;
-        check(mpenv_create(&c, &mgr_));
+        if (cfg.maps.empty()) {
+            check(mpenv_create(&c, &mgr_));
+        } else {
+            std::vector<mpenv_map_range> ranges;
+            for (const auto &m : cfg.maps) ranges.push_back({ m.first.c_str(), m.second });
+            check(mpenv_create_maps(&c, ranges.data(), (int32_t)ranges.size(), &mgr_));
+        }
         execMode_ = cfg.execMode;
         // mgr.cpp loads policyWeightsPath into the sim's policyWeights; a
         // checkpoint that does not load is an error, as the reference's asserts
@@ -230,6 +247,20 @@ public:
         int32_t mode = 0;
         check(mpenv_scene_residency(mgr_, &mode));
         return mode;
+    }
+    // extension: map sets (mpenv_maps.h): the number of ranges (1 for a single-map manager) and one of them
+    int numMaps() const
+    {
+        int32_t n = 0;
+        check(mpenv_num_maps(mgr_, &n));
+        return n;
+    }
+    MapInfo mapInfo(int range) const
+    {
+        mpenv_map_desc d;
+        const char *path = nullptr;
+        check(mpenv_map_info(mgr_, range, &d, &path));
+        return { path ? path : "", d.first_world, d.num_worlds, d.scene, d.residency };
     }
     // extension: the egocentric depth camera (mpenv_camera.h): per agent a [height][width] depth (f32) and
     // label (u8) image behind every step and init while enabled; width and height multiples of 8 in [8, 128],

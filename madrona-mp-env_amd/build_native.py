@@ -31,7 +31,7 @@ LIB_SOURCES = ["kernels.hip", "move.hip", "vis.hip", "obs.hip", "lidar.hip", "ho
                "policy.hip", "camera.hip", "manager.cpp", "manager_scene.cpp", "camera.cpp", "policy.cpp", "scene.cpp",
                "navmesh.cpp"]
 API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h", "mpenv_policy_precision.h",
-                                                     "mpenv_scene_residency.h", "mpenv_camera.h")]
+                                                     "mpenv_scene_residency.h", "mpenv_camera.h", "mpenv_maps.h")]
 MAX_PARALLEL = 16  # what one command may use on the GPU machines, whatever the machine's CPU count
 
 

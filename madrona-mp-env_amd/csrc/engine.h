@@ -497,6 +497,12 @@ struct StateTab {
     int32_t nSeg, W, nWide, nNarrow;
     uint32_t go;  // written by k_state_check, read by the load that follows it
     uint32_t err; // MPENV_STATE_ERR_* (mpenv_state_error reads and clears)
+    // Map sets (mpenv_maps.h): the range of each world (device, [W]) and the
+    // scene of each range; k_state_check refuses a world map that takes a
+    // world's state from a snapshot world of another scene.  Null for a
+    // single-map manager: nothing to check.
+    const int32_t *mapOfWorld;
+    int32_t rangeScene[MPENV_MAX_MAP_RANGES];
 };
 // throws std::runtime_error for a section whose buffer is not allocated (a
 // table buffer that is neither a section nor exempt fails state.hip's build)

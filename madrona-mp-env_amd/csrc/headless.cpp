@@ -3,6 +3,11 @@
 // print world-steps/s ("FPS") and agent-steps/s.
 //
 //   headless CUDA NUM_WORLDS NUM_STEPS SCENE_DIR [--rand-actions] [--team-size N] [--policy-weights DIR]
+//            [--map DIR:N]...
+//
+// --map DIR:N, repeatable, makes the batch a map set (mpenv_maps.h): N worlds
+// on DIR per option, in order; the counts sum to NUM_WORLDS and SCENE_DIR is
+// not read.
 //
 // --policy-weights loads a converted checkpoint (Config::policyWeightsPath)
 // and binds every agent to it: the frozen network picks the actions inside
@@ -42,10 +47,25 @@ int main(int argc, char *argv[])
     bool rand_actions = false;
     uint32_t team_size = 6;
     const char *weights = nullptr;
+    std::vector<std::pair<std::string, uint32_t>> maps;
     for (int i = 5; i < argc; i++) {
         if (!strcmp(argv[i], "--rand-actions")) rand_actions = true;
         else if (!strcmp(argv[i], "--team-size") && i + 1 < argc) team_size = (uint32_t)std::stoul(argv[++i]);
         else if (!strcmp(argv[i], "--policy-weights") && i + 1 < argc) weights = argv[++i];
+        else if (!strcmp(argv[i], "--map") && i + 1 < argc) {
+            const std::string a = argv[++i];
+            const size_t colon = a.rfind(':');
+            if (colon == std::string::npos || colon + 1 == a.size()) {
+                fprintf(stderr, "--map takes DIR:N, got %s\n", a.c_str());
+                return 1;
+            }
+            const std::string count = a.substr(colon + 1);
+            if (count.find_first_not_of("0123456789") != std::string::npos) {
+                fprintf(stderr, "--map takes DIR:N, got %s\n", a.c_str());
+                return 1;
+            }
+            maps.push_back({ a.substr(0, colon), (uint32_t)std::stoul(count) });
+        }
     }
     const std::string col = scene + "/collisions.bin", nav = scene + "/navmesh.bin",
                       spw = scene + "/spawns.bin", zon = scene + "/zones.bin";
@@ -63,6 +83,7 @@ int main(int argc, char *argv[])
         cfg.policyHistorySize = 1;
         cfg.map = { scene.c_str(), col.c_str(), nav.c_str(), spw.c_str(), zon.c_str(), Vector3::zero(), 0.f };
         cfg.policyWeightsPath = weights;
+        cfg.maps = maps;
         Manager mgr(cfg);
         mgr.init();
         if (weights) mgr.setUniformAgentPolicy(AgentPolicy { 0 });

@@ -151,14 +151,14 @@ void mpenv_manager::record(hipStream_t st)
 // The Step graph over one world range on one stream.  With timing on,
 // kNumTimedKernels + 1 events bracket the kernels (one segment per
 // range per step, contiguous in the pool).
-void mpenv_manager::stepRange(const DevState &R, const SceneDev &rsc, hipStream_t st)
+void mpenv_manager::stepRange(const DevState &R, const SceneDev &rsc, const SceneImages &img, hipStream_t st)
 {
     record(st);
     launched(launchMove(R, rsc, img, st), "k_move launch failed");
     record(st);
     launched(launchSimStep(R, rsc, img, st), "k_sim launch failed");
     record(st);
-    if (lidarBranch && groups == 1 && !timing) {
+    if (lidarBranch && groups == 1 && !timing && !mapSet()) {
         HIP_CHECK(hipEventRecord(bForkEv, st));
         bSide.startAfter(bForkEv);
         launched(launchLidar(R, rsc, img, lidarItersOf(R), bSide.stream), "k_lidar launch failed");
@@ -237,11 +237,20 @@ std::vector<char> mpenv_manager::argKey() const
     put(&groups, sizeof(groups));
     put(&lidarBranch, sizeof(lidarBranch));
     put(&lidarIters, sizeof(lidarIters));
+    // on a map-set manager nothing launches with these three (S is the
+    // whole batch, sc and img range 0's scene): a dead part of its key
     put(&S, sizeof(S));
     put(&sc, sizeof(sc));
     put(&img, sizeof(img));
     for (const DevState &G : gS) put(&G, sizeof(G));
     for (const SceneDev &g : gsc) put(&g, sizeof(g));
+    // a map set: every range's three structs (none for a single-map manager,
+    // whose key is the bytes above)
+    for (const MapRange &r : ranges) {
+        put(&r.S, sizeof(r.S));
+        put(&r.sc, sizeof(r.sc));
+        put(&scenes[r.scene].img, sizeof(SceneImages));
+    }
     return k;
 }
 
@@ -314,8 +323,13 @@ bool mpenv_manager::captureStep()
 
 void mpenv_manager::launchStepDirect(hipStream_t st)
 {
+    if (mapSet()) {
+        // the ranges are the groups: in range order on the one stream
+        for (const MapRange &r : ranges) stepRange(r.S, r.sc, scenes[r.scene].img, st);
+        return;
+    }
     if (groups <= 1) {
-        stepRange(S, sc, st);
+        stepRange(S, sc, img, st);
         return;
     }
     // group 0 runs on the caller's stream itself, so G groups occupy G
@@ -323,10 +337,10 @@ void mpenv_manager::launchStepDirect(hipStream_t st)
     HIP_CHECK(hipEventRecord(forkEv, st));
     for (int i = 1; i < groups; i++) gside[i].startAfter(forkEv);
     for (int i = 1; i < groups; i++) {
-        stepRange(gS[i], gsc[i], gside[i].stream);
+        stepRange(gS[i], gsc[i], img, gside[i].stream);
         gside[i].markDone();
     }
-    stepRange(gS[0], gsc[0], st);
+    stepRange(gS[0], gsc[0], img, st);
     for (int i = 1; i < groups; i++) gside[i].joinInto(st);
 }
 
@@ -335,10 +349,15 @@ void mpenv_manager::runInitGraph(hipStream_t st)
     // triggerReset on every world (mgr.cpp:1936-1938) then the Init graph
     // (sim.cpp:5322-5340): resetSystem + observations + lidar.
     HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)S.reset, 1, (size_t)S.W, st));
-    launched(launchResetOnly(S, sc, st), "k_reset launch failed");
-    launched(launchVisibility(S, sc, img, st), "k_vis launch failed");
-    launched(launchObservations(S, sc, st), "k_obs launch failed");
-    launched(launchLidar(S, sc, img, lidarItersOf(S), st), "k_lidar launch failed");
+    auto initRange = [&](const DevState &R, const SceneDev &rsc, const SceneImages &rimg) {
+        launched(launchResetOnly(R, rsc, st), "k_reset launch failed");
+        launched(launchVisibility(R, rsc, rimg, st), "k_vis launch failed");
+        launched(launchObservations(R, rsc, st), "k_obs launch failed");
+        launched(launchLidar(R, rsc, rimg, lidarItersOf(R), st), "k_lidar launch failed");
+    };
+    if (mapSet())
+        for (const MapRange &r : ranges) initRange(r.S, r.sc, scenes[r.scene].img);
+    else initRange(S, sc, img);
     if (camOn) renderCamera(st);
 }
 
@@ -605,10 +624,10 @@ int32_t mpenv_abi_version(void) { return MPENV_ABI_VERSION; }
 
 const char *mpenv_last_error(void) { return g_last_error.c_str(); }
 
-int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
+// mpenv_create (plan null: cfg->scene_path) and mpenv_create_maps (the
+// planned list, cfg->scene_path null).
+static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager **out)
 {
-    if (!cfg || !out) return fail(MPENV_ERR_INVALID, "null argument");
-    *out = nullptr;
     if (cfg->exec_mode != MPENV_EXEC_CUDA)
         return fail(MPENV_ERR_UNSUPPORTED, "ExecMode.CPU is not supported: this engine runs only on the GPU (HIP)");
     if (cfg->task_type != MPENV_TASK_ZONE && cfg->task_type != MPENV_TASK_ZONE_CAPTURE_DEFEND)
@@ -616,7 +635,7 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
     if (cfg->team_size < 1 || cfg->team_size > kMaxTeamSize)
         return fail(MPENV_ERR_INVALID, "team_size must be in [1, 6]");
     if (cfg->num_worlds == 0) return fail(MPENV_ERR_INVALID, "num_worlds must be > 0");
-    if (!cfg->scene_path) return fail(MPENV_ERR_INVALID, "scene_path is required");
+    if (!plan && !cfg->scene_path) return fail(MPENV_ERR_INVALID, "scene_path is required");
     if (cfg->sim_flags >> 12) return fail(MPENV_ERR_INVALID, "sim_flags has bits beyond SubZones (1 << 11)");
     if (cfg->replay_log_path && cfg->record_log_path)
         return fail(MPENV_ERR_UNSUPPORTED, "record and replay logs together are not supported");
@@ -633,17 +652,33 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
         m->S.outTab = nullptr;
         m->S.outBase = 0;
         m->cfg = *cfg;
-        m->scenePath = cfg->scene_path;
+        m->scenePath = plan ? plan->scenes[plan->ranges[0].scene].path : std::string(cfg->scene_path);
         m->cfg.scene_path = m->scenePath.c_str();
         m->gpu = cfg->gpu_id;
         // A blocking stream: ordered after work the caller queued on the
         // legacy default stream (e.g. torch writes into the action tensors),
         // matching the synchronous Manager::step contract (mgr.cpp:1949-1960).
         m->stream = Stream::create(hipStreamDefault);
-        m->scene = loadScene(m->scenePath, (cfg->sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
-        m->limits = sceneLimits(m->scene);
-        if (!m->limits.supported) return fail(MPENV_ERR_UNSUPPORTED, "scene not supported: " + m->limits.reason);
-        buildSceneDev(*m);
+        if (plan) {
+            // the per-scene device work once per loaded scene; spawnTrackLen,
+            // a row shape of the buffer table, is the set's largest in every
+            // SceneDev (a range whose own value is smaller leaves the rows'
+            // tails at their reset fill)
+            m->scenes = std::move(plan->scenes);
+            for (MapScene &ms : m->scenes) {
+                buildSceneDev(*m, ms.scene, ms.limits, ms.sc, ms.img);
+                ms.sc.spawnTrackLen = plan->spawnTrackLen;
+            }
+            const MapScene &first = m->scenes[plan->ranges[0].scene];
+            m->sc = first.sc;
+            m->img = first.img;
+            m->limits = first.limits;
+        } else {
+            m->scene = loadScene(m->scenePath, (cfg->sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
+            m->limits = sceneLimits(m->scene);
+            if (!m->limits.supported) return fail(MPENV_ERR_UNSUPPORTED, "scene not supported: " + m->limits.reason);
+            buildSceneDev(*m, m->scene, m->limits, m->sc, m->img);
+        }
         m->S.W = (int32_t)cfg->num_worlds;
         m->S.T = (int32_t)cfg->team_size;
         m->S.N = 2 * m->S.T;
@@ -659,6 +694,34 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
                                                  : nullptr;
         m->stateTabDev = m->alloc<StateTab>(1);
         buildStateTab(m->S, m->sc, m->stateTabDev, m->stateTab);
+        if (plan) {
+            // the ranges as complete engines, the world -> range table, and
+            // the checkpoint header's hash of the layout (reserved[0..1];
+            // zeros for a single-map manager): FNV-1a 64 over each range's
+            // world count and its scene's collisions.bin hash
+            std::vector<int32_t> mow((size_t)m->S.W);
+            uint64_t h = 1469598103934665603ull;
+            auto mix = [&h](uint64_t v) {
+                for (int b = 0; b < 8; b++) {
+                    h ^= (v >> (8 * b)) & 0xffu;
+                    h *= 1099511628211ull;
+                }
+            };
+            for (size_t k = 0; k < plan->ranges.size(); k++) {
+                MapRange r = plan->ranges[k];
+                sliceState(m->S, m->scenes[r.scene].sc, r.w0, r.n, r.S, r.sc);
+                m->ranges.push_back(r);
+                std::fill(mow.begin() + r.w0, mow.begin() + r.w0 + r.n, (int32_t)k);
+                m->stateTab.rangeScene[k] = r.scene;
+                mix((uint64_t)r.n);
+                mix(m->scenes[r.scene].collisionsHash);
+            }
+            m->mapOfWorld = m->alloc<int32_t>(mow.size());
+            m->upload(m->mapOfWorld, mow.data(), mow.size() * sizeof(int32_t));
+            m->stateTab.mapOfWorld = m->mapOfWorld;
+            m->stateTab.hdr.reserved[0] = (uint32_t)h;
+            m->stateTab.hdr.reserved[1] = (uint32_t)(h >> 32);
+        }
         m->upload(m->stateTabDev, &m->stateTab, sizeof(StateTab));
         // the caller's path strings are not kept past create
         m->cfg.replay_log_path = m->cfg.record_log_path = m->cfg.event_log_path = nullptr;
@@ -671,7 +734,7 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
             // 1.215; profiles/r05e_ab_world_groups.jsonl).
             int want = 1;
             if (const char *e = std::getenv("MPENV_WORLD_GROUPS")) want = std::atoi(e);
-            m->setupGroups(want);
+            m->setupGroups(plan ? 1 : want); // a map set's ranges are its groups
         }
         if (const char *e = std::getenv("MPENV_SCENE_RESIDENCY")) {
             const std::string v = e;
@@ -682,18 +745,93 @@ int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
                 throw std::runtime_error("MPENV_SCENE_RESIDENCY=" + v + ": " + g_last_error);
         }
         if (const char *e = std::getenv("MPENV_STEP_GRAPH")) m->useGraph = std::atoi(e) != 0;
-        if (const char *e = std::getenv("MPENV_LIDAR_BRANCH"))
+        if (const char *e = plan ? nullptr : std::getenv("MPENV_LIDAR_BRANCH"))
             if (std::atoi(e) != 0 && mpenv_set_lidar_branch(m.get(), 1) != MPENV_OK) throw std::runtime_error(g_last_error);
         // TrainControl from sim flags (mgr.cpp:1397-1413)
         int32_t tc[3] = { (cfg->sim_flags & MPENV_SIMFLAG_SIM_EVAL_MODE) ? 1 : 0,
                           (cfg->sim_flags & MPENV_SIMFLAG_STAGGER_STARTS) ? 1 : 0,
                           (cfg->sim_flags & MPENV_SIMFLAG_RANDOM_FLIP_TEAMS) ? 1 : 0 };
         HIP_CHECK(hipMemcpyAsync(m->S.trainCtrl, tc, sizeof(tc), hipMemcpyHostToDevice, m->stream));
-        launched(launchConstruct(m->S, m->sc, tc, m->stream), "construct launch failed");
+        if (m->mapSet())
+            for (const MapRange &r : m->ranges) launched(launchConstruct(r.S, r.sc, tc, m->stream), "construct launch failed");
+        else launched(launchConstruct(m->S, m->sc, tc, m->stream), "construct launch failed");
         HIP_CHECK(hipStreamSynchronize(m->stream));
         liveAdd(m.get());
         *out = m.release();
         return MPENV_OK;
+    });
+}
+
+int mpenv_create(const mpenv_config *cfg, mpenv_manager **out)
+{
+    if (!cfg || !out) return fail(MPENV_ERR_INVALID, "null argument");
+    *out = nullptr;
+    return createManager(cfg, nullptr, out);
+}
+
+// Map sets (mpenv_maps.h; DESIGN.md §2 definition 19)
+int mpenv_create_maps(const mpenv_config *cfg, const mpenv_map_range *maps, int32_t n, mpenv_manager **out)
+{
+    if (!cfg || !maps || !out) return fail(MPENV_ERR_INVALID, "null argument");
+    *out = nullptr;
+    for (const char *p : { cfg->replay_log_path, cfg->record_log_path, cfg->event_log_path, cfg->curriculum_data_path })
+        if (p)
+            return fail(MPENV_ERR_UNSUPPORTED, "map set: replay_log_path, record_log_path, event_log_path and "
+                                               "curriculum_data_path are not supported (logged and snapshot "
+                                               "positions belong to one map)");
+    MapPlan plan;
+    const int rc = guarded([&]() -> int { return planMaps(*cfg, maps, n, plan, nullptr); }, MPENV_ERR_INVALID);
+    if (rc != MPENV_OK) return rc;
+    return createManager(cfg, &plan, out);
+}
+
+static int mapSetRefused(const mpenv_manager *m, const char *what, const char *why)
+{
+    if (!m->mapSet()) return MPENV_OK;
+    return fail(MPENV_ERR_UNSUPPORTED, std::string(what) + " is not supported on a map-set manager: " + why);
+}
+
+int mpenv_num_maps(mpenv_manager *m, int32_t *n)
+{
+    if (!m || !n) return fail(MPENV_ERR_INVALID, "null argument");
+    *n = m->mapSet() ? (int32_t)m->ranges.size() : 1;
+    return MPENV_OK;
+}
+
+int mpenv_map_info(mpenv_manager *m, int32_t range, mpenv_map_desc *out, const char **scene_path)
+{
+    if (!m || !out) return fail(MPENV_ERR_INVALID, "null argument");
+    const int32_t n = m->mapSet() ? (int32_t)m->ranges.size() : 1;
+    if (range < 0 || range >= n)
+        return fail(MPENV_ERR_INVALID, "map range " + std::to_string(range) + " is outside [0, " + std::to_string(n) + ")");
+    std::memset(out, 0, sizeof(*out));
+    out->supported = 1;
+    const SceneImages *img = &m->img;
+    if (m->mapSet()) {
+        const MapRange &r = m->ranges[(size_t)range];
+        out->first_world = r.w0;
+        out->num_worlds = r.n;
+        out->scene = r.scene;
+        img = &m->scenes[r.scene].img;
+        if (scene_path) *scene_path = m->scenes[r.scene].path.c_str();
+    } else {
+        out->num_worlds = m->S.W;
+        if (scene_path) *scene_path = m->scenePath.c_str();
+    }
+    out->residency = img->residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+    return MPENV_OK;
+}
+
+int mpenv_map_of_world(mpenv_manager *m, void **dev_ptr)
+{
+    if (!m || !dev_ptr) return fail(MPENV_ERR_INVALID, "null argument");
+    return guarded([&] {
+        // a single-map manager: all zeros, made on first use
+        if (!m->mapOfWorld) {
+            m->mapOfWorld = m->alloc<int32_t>((size_t)m->S.W);
+            HIP_CHECK(hipStreamSynchronize(m->stream));
+        }
+        *dev_ptr = m->mapOfWorld;
     });
 }
 
@@ -1043,9 +1181,12 @@ void mpenv_xla_gpu_stream_step_status(void *stream, void **buffers, const char *
 int64_t mpenv_xla_errors(void) { return g_xlaErrors.load(); }
 
 // Learner exchange wire format (wire.hip)
+static const char *const kWireWhy = "the message is one view over the batch and its observation kernel takes one scene "
+                                    "(the gather and local exchanges work)";
 int mpenv_wire_bytes(mpenv_manager *m, int32_t keyframe, int64_t *bytes)
 {
     if (!m || !bytes) return fail(MPENV_ERR_INVALID, "null argument");
+    if (int rc = mapSetRefused(m, "mpenv_wire_bytes", kWireWhy)) return rc;
     *bytes = wireBytes(m->S, keyframe != 0);
     return MPENV_OK;
 }
@@ -1053,6 +1194,7 @@ int mpenv_wire_bytes(mpenv_manager *m, int32_t keyframe, int64_t *bytes)
 int mpenv_wire_pack(mpenv_manager *m, void *dst, int32_t keyframe, void *stream)
 {
     if (!m || !dst) return fail(MPENV_ERR_INVALID, "null argument");
+    if (int rc = mapSetRefused(m, "mpenv_wire_pack", kWireWhy)) return rc;
     if ((uintptr_t)dst & 15u) return fail(MPENV_ERR_INVALID, "wire message buffer must be 16-B aligned");
     if (launchWirePack(m->S, static_cast<char *>(dst), keyframe != 0, m->sc.worldOffset, streamOf(m, stream)))
         return fail(MPENV_ERR_HIP, "wire pack launch failed");
@@ -1062,6 +1204,7 @@ int mpenv_wire_pack(mpenv_manager *m, void *dst, int32_t keyframe, void *stream)
 int mpenv_wire_unpack(mpenv_manager *m, const void *src, int32_t keyframe, void *stream)
 {
     if (!m || !src) return fail(MPENV_ERR_INVALID, "null argument");
+    if (int rc = mapSetRefused(m, "mpenv_wire_unpack", kWireWhy)) return rc;
     if ((uintptr_t)src & 15u) return fail(MPENV_ERR_INVALID, "wire message buffer must be 16-B aligned");
     void *st = streamOf(m, stream);
     const int W = m->S.W;
@@ -1413,6 +1556,8 @@ int mpenv_graph_status(mpenv_manager *m, int32_t *graph_on, char *reason, int32_
 int mpenv_set_lidar_branch(mpenv_manager *m, int32_t on)
 {
     if (!m) return fail(MPENV_ERR_INVALID, "null argument");
+    if (on)
+        if (int rc = mapSetRefused(m, "mpenv_set_lidar_branch", "the ranges' kernels run in order on one stream")) return rc;
     return guarded([&] {
         HIP_CHECK(hipStreamSynchronize(m->stream));
         if (on) ensureSide(m->bSide, m->bForkEv);
@@ -1433,6 +1578,9 @@ int mpenv_set_lidar_iters(mpenv_manager *m, int32_t n)
 int mpenv_set_world_groups(mpenv_manager *m, int32_t groups)
 {
     if (!m || groups < 1) return fail(MPENV_ERR_INVALID, "bad argument");
+    if (groups > 1)
+        if (int rc = mapSetRefused(m, "mpenv_set_world_groups", "the ranges are the groups and run in order on one stream"))
+            return rc;
     return guarded([&] {
         HIP_CHECK(hipStreamSynchronize(m->stream));
         m->setupGroups(groups);
@@ -1445,21 +1593,34 @@ int mpenv_set_scene_residency(mpenv_manager *m, int32_t mode)
     if (mode != MPENV_SCENE_AUTO && mode != MPENV_SCENE_LDS && mode != MPENV_SCENE_GLOBAL)
         return fail(MPENV_ERR_INVALID, "scene residency must be MPENV_SCENE_AUTO, MPENV_SCENE_LDS or MPENV_SCENE_GLOBAL "
                                        "(MPENV_SCENE_RESIDENCY=auto|lds|global)");
-    if (mode == MPENV_SCENE_LDS && !m->limits.ldsOk)
+    if (mode == MPENV_SCENE_LDS && !m->limits.ldsOk && !m->mapSet())
         return fail(MPENV_ERR_INVALID, "scene does not fit the LDS-resident path: " + m->limits.ldsWhyNot);
+    // a map set: every scene, or (one that does not fit, named) none
+    for (size_t r = 0; mode == MPENV_SCENE_LDS && r < m->ranges.size(); r++) {
+        const MapScene &ms = m->scenes[m->ranges[r].scene];
+        if (!ms.limits.ldsOk)
+            return fail(MPENV_ERR_INVALID, "map range " + std::to_string(r) + " (" + ms.path +
+                                               ") does not fit the LDS-resident path: " + ms.limits.ldsWhyNot);
+    }
     return guarded([&] {
         // the kernels of a step in flight keep the path they were launched
-        // on; the step graph is keyed on m->img (argKey) and re-captured
+        // on; the step graph is keyed on every img (argKey) and re-captured
         HIP_CHECK(hipStreamSynchronize(m->stream));
         m->residencyMode = mode;
-        const bool lds = mode == MPENV_SCENE_LDS || (mode == MPENV_SCENE_AUTO && m->limits.ldsOk);
-        m->img.residency = lds ? kResidencyLds : kResidencyGlobal;
+        auto pick = [mode](const SceneLimits &l) {
+            const bool lds = mode == MPENV_SCENE_LDS || (mode == MPENV_SCENE_AUTO && l.ldsOk);
+            return lds ? kResidencyLds : kResidencyGlobal;
+        };
+        m->img.residency = pick(m->limits); // a map set: range 0's scene, as the test hooks read it
+        for (MapScene &ms : m->scenes) ms.img.residency = pick(ms.limits);
     });
 }
 
 int mpenv_scene_residency(mpenv_manager *m, int32_t *mode_in_use)
 {
     if (!m || !mode_in_use) return fail(MPENV_ERR_INVALID, "null argument");
+    if (m->mapSet())
+        return fail(MPENV_ERR_INVALID, "mpenv_scene_residency: a map set has a residency per map (mpenv_map_info)");
     *mode_in_use = m->img.residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
     return MPENV_OK;
 }
@@ -1594,6 +1755,7 @@ int mpenv_enable_stats(mpenv_manager *m, int32_t enable)
         unsigned long long *p = enable ? m->statsBuf : nullptr;
         m->S.stats = p;
         for (DevState &G : m->gS) G.stats = p;
+        for (MapRange &r : m->ranges) r.S.stats = p;
     });
 }
 
@@ -1629,6 +1791,9 @@ int mpenv_kernel_timings(mpenv_manager *m, int32_t max_n, const char **names, fl
             }
             steps++;
         }
+        // a map set records one segment per range and step: each kernel's
+        // time is summed over the ranges
+        if (m->mapSet()) steps /= (int)m->ranges.size();
         m->eventsUsed = 0;
         for (int k = 0; k < nk && k < max_n; k++) {
             if (names) names[k] = kernelName(k);

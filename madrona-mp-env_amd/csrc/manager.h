@@ -24,9 +24,6 @@ using namespace mpenv;
 namespace mpenv {
 // Sets this thread's mpenv_last_error text and returns `code` (manager.cpp).
 int fail(int code, const std::string &msg);
-// manager_scene.cpp: the scene's device image (m.sc and its buffers) from
-// m.scene and m.cfg.
-void buildSceneDev(mpenv_manager &m);
 // manager_scene.cpp: which residency a scene can have -- the one place that
 // decides it, for mpenv_create, mpenv_set_scene_residency and mpenv_scene_info.
 struct SceneLimits {
@@ -39,6 +36,39 @@ struct SceneLimits {
     std::string reason;     // !supported: why
 };
 SceneLimits sceneLimits(const Scene &s);
+// manager_scene.cpp: a scene's device image (`sc`, `img` and their buffers,
+// owned by m) from the loaded scene, its limits and m.cfg.
+void buildSceneDev(mpenv_manager &m, const Scene &s, const SceneLimits &limits, SceneDev &sc, SceneImages &img);
+// manager_scene.cpp: why cfg's task or flags rule the scene out ("": they do not)
+std::string sceneTaskProblem(const Scene &s, const mpenv_config &cfg);
+
+// Map sets (mpenv_maps.h; DESIGN.md §2 definition 19).  One loaded scene: what
+// a single-map manager keeps in scenePath / scene / sc / img / limits.  sc
+// holds the manager's world_id_offset and the set's common spawnTrackLen.
+struct MapScene {
+    std::string path;
+    Scene scene;
+    SceneDev sc;
+    SceneImages img {};
+    SceneLimits limits;
+    uint64_t collisionsHash = 0; // FNV-1a 64 of collisions.bin (scene.h)
+};
+// One range: worlds [w0, w0 + n) as a complete engine (sliceState) on scenes[scene]
+struct MapRange {
+    int32_t scene = 0, w0 = 0, n = 0;
+    DevState S {};
+    SceneDev sc {};
+};
+// manager_scene.cpp: what mpenv_create_maps and mpenv_maps_plan make of a
+// list, without a GPU.  Returns MPENV_OK or the refusal's code (its message
+// is in mpenv_last_error; `desc`, when not null, is filled as far as the list
+// was read).
+struct MapPlan {
+    std::vector<MapScene> scenes; // loaded, limits set; no device image yet
+    std::vector<MapRange> ranges; // scene, w0, n
+    int32_t spawnTrackLen = 0;    // the largest of the scenes'
+};
+int planMaps(const mpenv_config &cfg, const mpenv_map_range *maps, int32_t n, MapPlan &plan, mpenv_map_desc *desc);
 } // namespace mpenv
 
 #define HIP_CHECK(expr)                                                                   \
@@ -183,6 +213,15 @@ struct mpenv_manager {
     DevState S;
     Stream stream;
     std::vector<void *> allocations;
+    // Map sets: empty for a manager from mpenv_create, which runs on the
+    // members above alone.  For one from mpenv_create_maps the step, the
+    // init, the construct and the camera loop over `ranges` in order on the
+    // call's stream, and sc / img / limits / scenePath above are range 0's
+    // scene (the ray and geometry test hooks answer for it).
+    std::vector<MapScene> scenes;
+    std::vector<MapRange> ranges;
+    int32_t *mapOfWorld = nullptr; // device [W]: range index per world (mpenv_map_of_world)
+    bool mapSet() const { return !ranges.empty(); }
 
     // Debug gather buffers (allocated lazily)
     float *dbgAF = nullptr, *dbgWF = nullptr, *dbgCrumbs = nullptr;
@@ -308,7 +347,7 @@ struct mpenv_manager {
     void allocPolicyWork();
     void setPolicySlot(int slot, const float *blob);
     void record(hipStream_t st);
-    void stepRange(const DevState &R, const SceneDev &rsc, hipStream_t st);
+    void stepRange(const DevState &R, const SceneDev &rsc, const SceneImages &rimg, hipStream_t st);
     void preStep(hipStream_t st);
     void postStep(hipStream_t st);
     void runStep(hipStream_t st);

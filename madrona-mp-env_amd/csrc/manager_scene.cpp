@@ -104,18 +104,29 @@ SceneLimits mpenv::sceneLimits(const Scene &s)
     return l;
 }
 
-void mpenv::buildSceneDev(mpenv_manager &m)
+// What buildSceneDev refuses for the task and flags, decided from the host
+// scene alone (mpenv_maps_plan answers without a GPU).
+std::string mpenv::sceneTaskProblem(const Scene &s, const mpenv_config &cfg)
 {
-    Scene &s = m.scene;
-    SceneDev &sc = m.sc;
-    std::memset(&sc, 0, sizeof(sc));
-    if (!m.limits.supported) throw std::runtime_error("scene not supported: " + m.limits.reason);
-    if (s.zoneAABBs.empty() || s.zoneAABBs.size() > (size_t)kMaxZones) throw std::runtime_error("bad zone count");
-    if (s.numDefaultASpawns == 0 || s.numDefaultBSpawns == 0) throw std::runtime_error("scene needs A and B spawns");
-    if ((m.cfg.sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) &&
+    if (s.zoneAABBs.empty() || s.zoneAABBs.size() > (size_t)kMaxZones) return "bad zone count";
+    if (s.numDefaultASpawns == 0 || s.numDefaultBSpawns == 0) return "scene needs A and B spawns";
+    if ((cfg.sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) &&
         (s.aSpawns.size() == s.numDefaultASpawns || s.bSpawns.size() == s.numDefaultBSpawns))
         // the reference would index past its spawn array here (utils.cpp:358-366)
-        throw std::runtime_error("SpawnInMiddle: no free middle cells in this scene");
+        return "SpawnInMiddle: no free middle cells in this scene";
+    // initWorld starts every ZoneCaptureDefend episode at zone 3 (sim.cpp:822-825)
+    if (cfg.task_type == MPENV_TASK_ZONE_CAPTURE_DEFEND && s.zoneAABBs.size() < 4)
+        return "ZoneCaptureDefend needs a scene with >= 4 zones";
+    // sub-zones 0 and 1 are zones 1 and 2 (level_gen.cpp:283-293)
+    if ((cfg.sim_flags & MPENV_SIMFLAG_SUB_ZONES) && s.zoneAABBs.size() < 3) return "SubZones needs a scene with >= 3 zones";
+    return "";
+}
+
+void mpenv::buildSceneDev(mpenv_manager &m, const Scene &s, const SceneLimits &limits, SceneDev &sc, SceneImages &img)
+{
+    std::memset(&sc, 0, sizeof(sc));
+    if (!limits.supported) throw std::runtime_error("scene not supported: " + limits.reason);
+    if (const std::string why = sceneTaskProblem(s, m.cfg); !why.empty()) throw std::runtime_error(why);
 
     BVHNode *d_nodes = m.alloc<BVHNode>(s.nodes.size());
     m.upload(d_nodes, s.nodes.data(), sizeof(BVHNode) * s.nodes.size());
@@ -242,12 +253,7 @@ void mpenv::buildSceneDev(mpenv_manager &m)
         }
         sc.numSnapshots = (int32_t)snaps.size();
     }
-    // initWorld starts every ZoneCaptureDefend episode at zone 3 (sim.cpp:822-825)
-    if (sc.task == MPENV_TASK_ZONE_CAPTURE_DEFEND && s.zoneAABBs.size() < 4)
-        throw std::runtime_error("ZoneCaptureDefend needs a scene with >= 4 zones");
     if (m.cfg.sim_flags & MPENV_SIMFLAG_SUB_ZONES) {
-        // sub-zones 0 and 1 are zones 1 and 2 (level_gen.cpp:283-293)
-        if (s.zoneAABBs.size() < 3) throw std::runtime_error("SubZones needs a scene with >= 3 zones");
         mp::subZoneTable(s.zoneAABBs.data(), s.zoneRotations.data(), sc.subZones);
     }
     for (int z = 0; z < sc.numZones; z++) {
@@ -286,10 +292,10 @@ void mpenv::buildSceneDev(mpenv_manager &m)
     {
         // the global-resident images, whichever path is in use: switching
         // residency later allocates nothing
-        m.img.sphere = m.alloc<char>(bvhLdsBytesSphere(sc));
-        m.img.oct = m.alloc<char>(bvhLdsBytesOct(sc));
-        m.img.residency = m.limits.ldsOk ? kResidencyLds : kResidencyGlobal;
-        launched(buildSceneImages(sc, m.img, m.stream), "k_scene_images launch failed");
+        img.sphere = m.alloc<char>(bvhLdsBytesSphere(sc));
+        img.oct = m.alloc<char>(bvhLdsBytesOct(sc));
+        img.residency = limits.ldsOk ? kResidencyLds : kResidencyGlobal;
+        launched(buildSceneImages(sc, img, m.stream), "k_scene_images launch failed");
     }
     sc.simFlags = m.cfg.sim_flags;
     sc.autoReset = m.cfg.auto_reset;
@@ -298,9 +304,89 @@ void mpenv::buildSceneDev(mpenv_manager &m)
     sc.initRandKey = mp::splitI(mp::initKey(m.cfg.rand_seed), 0);
 }
 
+// Map sets: the list as mpenv_create_maps will hold it.  Every refusal names
+// the range index and its directory.  Equal paths load once.
+int mpenv::planMaps(const mpenv_config &cfg, const mpenv_map_range *maps, int32_t n, MapPlan &plan, mpenv_map_desc *desc)
+{
+    if (desc)
+        for (int32_t r = 0; r < n && r < MPENV_MAX_MAP_RANGES; r++) std::memset(&desc[r], 0, sizeof(desc[r]));
+    if (cfg.scene_path) return fail(MPENV_ERR_INVALID, "map set: scene_path must be null when a map list is given");
+    if (n < 1 || n > MPENV_MAX_MAP_RANGES)
+        return fail(MPENV_ERR_INVALID, "map set: " + std::to_string(n) + " ranges (1 to " +
+                                           std::to_string(MPENV_MAX_MAP_RANGES) + ")");
+    auto where = [&](int32_t r) {
+        return "map range " + std::to_string(r) + " (" + (maps[r].scene_path ? maps[r].scene_path : "null") + ")";
+    };
+    uint64_t sum = 0;
+    for (int32_t r = 0; r < n; r++) {
+        if (!maps[r].scene_path) return fail(MPENV_ERR_INVALID, where(r) + ": scene_path is null");
+        if (maps[r].num_worlds == 0) return fail(MPENV_ERR_INVALID, where(r) + ": a range needs at least one world");
+        sum += maps[r].num_worlds;
+    }
+    if (sum != cfg.num_worlds)
+        return fail(MPENV_ERR_INVALID, "map set: the ranges hold " + std::to_string(sum) + " worlds, num_worlds is " +
+                                           std::to_string(cfg.num_worlds));
+    int rc = MPENV_OK;
+    std::string firstWhy;
+    int32_t w0 = 0;
+    for (int32_t r = 0; r < n; r++) {
+        const std::string path = maps[r].scene_path;
+        size_t si = 0;
+        while (si < plan.scenes.size() && plan.scenes[si].path != path) si++;
+        if (si == plan.scenes.size()) {
+            MapScene ms;
+            ms.path = path;
+            try {
+                ms.scene = loadScene(path, (cfg.sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
+            } catch (const std::exception &e) {
+                return fail(MPENV_ERR_IO, where(r) + ": " + e.what());
+            }
+            ms.limits = sceneLimits(ms.scene);
+            ms.collisionsHash = fnv1a64File(path + "/collisions.bin");
+            plan.scenes.push_back(std::move(ms));
+        }
+        const MapScene &ms = plan.scenes[si];
+        std::string why = ms.limits.supported ? sceneTaskProblem(ms.scene, cfg) : "scene not supported: " + ms.limits.reason;
+        if (desc) {
+            desc[r].first_world = w0;
+            desc[r].num_worlds = (int32_t)maps[r].num_worlds;
+            desc[r].scene = (int32_t)si;
+            desc[r].supported = why.empty() ? 1 : 0;
+            desc[r].residency = !why.empty() ? MPENV_SCENE_AUTO : ms.limits.ldsOk ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+            std::snprintf(desc[r].reason, sizeof(desc[r].reason), "%s", why.empty() ? ms.limits.ldsWhyNot.c_str() : why.c_str());
+        }
+        if (!why.empty() && rc == MPENV_OK) {
+            rc = MPENV_ERR_INVALID;
+            firstWhy = where(r) + ": " + why;
+        }
+        MapRange mr;
+        mr.scene = (int32_t)si;
+        mr.w0 = w0;
+        mr.n = (int32_t)maps[r].num_worlds;
+        plan.ranges.push_back(mr);
+        w0 += mr.n;
+        const Scene &s = ms.scene;
+        plan.spawnTrackLen = (int32_t)std::max<size_t>(
+            { (size_t)plan.spawnTrackLen, (size_t)kMinSpawnTrack, s.aSpawns.size(), s.bSpawns.size(), s.commonRespawns.size() });
+    }
+    return rc == MPENV_OK ? MPENV_OK : fail(rc, firstWhy);
+}
+
 // The queries below load the scene themselves and touch no GPU; whatever
 // the load throws is an I/O error to their callers.
 extern "C" {
+
+int mpenv_maps_plan(const mpenv_config *cfg, const mpenv_map_range *maps, int32_t n, mpenv_map_desc *out,
+                    int32_t *spawn_track_len)
+{
+    if (!cfg || !maps) return fail(MPENV_ERR_INVALID, "null argument");
+    return guarded([&]() -> int {
+        MapPlan plan;
+        const int rc = planMaps(*cfg, maps, n, plan, out);
+        if (spawn_track_len) *spawn_track_len = plan.spawnTrackLen;
+        return rc;
+    }, MPENV_ERR_INVALID);
+}
 
 // Host-side access to the navmesh and A* table (tests / oracle input).
 int mpenv_scene_navmesh(const char *scene_path, float *tri_verts_out, int32_t *num_tris, int32_t *adj_out,

@@ -10,6 +10,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -137,6 +138,26 @@ enum SimFlagsE : uint32_t {
     SimFlagsE_SubZones = 1u << 11,
 };
 
+// scene_path as a map set (mpenv_maps.h): a sequence of (directory, number of
+// worlds); `paths` keeps the strings the ranges point into.
+std::vector<mpenv_map_range> mapRanges(const py::object &list, std::vector<std::string> &paths)
+{
+    for (py::handle item : list) {
+        const py::sequence pair = py::reinterpret_borrow<py::sequence>(item);
+        if (py::len(pair) != 2) throw py::value_error("a map set is a list of (scene directory, number of worlds)");
+        paths.push_back(py::str(pair[0]));
+    }
+    std::vector<mpenv_map_range> ranges;
+    size_t k = 0;
+    for (py::handle item : list) {
+        const py::sequence pair = py::reinterpret_borrow<py::sequence>(item);
+        ranges.push_back({ paths[k++].c_str(), pair[1].cast<uint32_t>() });
+    }
+    return ranges;
+}
+
+const char *residencyName(int32_t mode) { return mode == MPENV_SCENE_LDS ? "lds" : "global"; }
+
 // The flat buffer array of gpuStreamInit / gpuStreamStep: exactly one
 // pointer per trainInterface input and output (the C ABI reads that many).
 std::vector<void *> streamBuffers(const std::vector<uintptr_t> &bufs)
@@ -214,12 +235,18 @@ PYBIND11_MODULE(madrona_mp_env, m)
     py::class_<PySimManager>(m, "SimManager")
         .def(py::init([precision_of](ExecMode exec_mode, int64_t gpu_id, int64_t num_worlds, int64_t rand_seed, bool auto_reset,
                          uint32_t sim_flags, Task task, uint32_t team_size, uint32_t num_pbt_policies,
-                         uint32_t policy_history_size, const std::string &scene_path, bool train_flank,
+                         uint32_t policy_history_size, py::object scene_path, bool train_flank,
                          py::object replay_log_path, py::object record_log_path, py::object event_log_path,
                          py::object curriculum_data_path, uint32_t world_id_offset,
                          py::object policy_weights_path, const std::string &policy_precision) {
                  const int32_t precision = precision_of(policy_precision);
-                 std::string replay, record, event, curric, weights;
+                 std::string replay, record, event, curric, weights, scene;
+                 // a str: one scene directory; a list of (directory, worlds): a map set (mpenv_maps.h)
+                 std::vector<std::string> map_paths;
+                 std::vector<mpenv_map_range> ranges;
+                 const bool map_set = !py::isinstance<py::str>(scene_path);
+                 if (map_set) ranges = mapRanges(scene_path, map_paths);
+                 else scene = py::str(scene_path);
                  mpenv_config cfg = {};
                  cfg.exec_mode = (int32_t)exec_mode;
                  cfg.gpu_id = (int32_t)gpu_id;
@@ -231,7 +258,7 @@ PYBIND11_MODULE(madrona_mp_env, m)
                  cfg.team_size = team_size;
                  cfg.num_pbt_policies = num_pbt_policies;
                  cfg.policy_history_size = policy_history_size;
-                 cfg.scene_path = scene_path.c_str();
+                 cfg.scene_path = map_set ? nullptr : scene.c_str();
                  cfg.train_flank = train_flank ? 1 : 0;
                  if (!replay_log_path.is_none()) { replay = py::str(replay_log_path); cfg.replay_log_path = replay.c_str(); }
                  if (!record_log_path.is_none()) { record = py::str(record_log_path); cfg.record_log_path = record.c_str(); }
@@ -244,7 +271,8 @@ PYBIND11_MODULE(madrona_mp_env, m)
                  auto h = std::make_shared<ManagerHandle>();
                  {
                      py::gil_scoped_release nogil;
-                     check(mpenv_create(&cfg, &h->mgr));
+                     check(map_set ? mpenv_create_maps(&cfg, ranges.data(), (int32_t)ranges.size(), &h->mgr)
+                                   : mpenv_create(&cfg, &h->mgr));
                  }
                  check(mpenv_policy_set_precision(h->mgr, precision));
                  // Manager::Config::policyWeightsPath (mgr.hpp:49): loaded after the create, failing loudly;
@@ -387,6 +415,36 @@ PYBIND11_MODULE(madrona_mp_env, m)
             int32_t mode = 0;
             check(mpenv_scene_residency(s.h->mgr, &mode));
             return std::string(mode == MPENV_SCENE_LDS ? "lds" : "global");
+        })
+        // map sets (mpenv_maps.h): the ranges as the engine holds them (one for a single-map manager), and
+        // the range index of every world as a zero-copy int32 [W]: the engine's own table, to be read only
+        .def("maps", [](PySimManager &s) {
+            int32_t n = 0;
+            check(mpenv_num_maps(s.h->mgr, &n));
+            py::list out;
+            for (int32_t r = 0; r < n; r++) {
+                mpenv_map_desc d;
+                const char *path = nullptr;
+                check(mpenv_map_info(s.h->mgr, r, &d, &path));
+                out.append(py::dict(py::arg("path") = std::string(path ? path : ""), py::arg("first_world") = d.first_world,
+                                    py::arg("num_worlds") = d.num_worlds, py::arg("scene") = d.scene,
+                                    py::arg("residency") = residencyName(d.residency)));
+            }
+            return out;
+        })
+        .def("world_map_tensor", [](PySimManager &s) {
+            PyTensor t;
+            t.owner = s.h;
+            t.dtype = MPENV_DTYPE_INT32;
+            check(mpenv_map_of_world(s.h->mgr, &t.ptr));
+            int32_t w = 0, n = 0;
+            check(mpenv_dims(s.h->mgr, &w, &n));
+            t.dims = { w };
+            int32_t nd = 0, dt = 0;
+            int64_t dims[8];
+            void *unused = nullptr;
+            check(mpenv_export_tensor(s.h->mgr, MPENV_EXPORT_RESET, &unused, &dt, &nd, dims, &t.gpu)); // the device id
+            return t;
         })
         // the egocentric depth camera (mpenv_camera.h): per agent a [height][width] depth (float32) and
         // label (uint8: 0 nothing, 1 map, 2 teammate, 3 opponent) image, rendered behind every step and
@@ -603,6 +661,27 @@ PYBIND11_MODULE(madrona_mp_env, m)
         return py::make_tuple(org, dir);
     }, py::arg("width"), py::arg("height"), py::arg("hfov_deg"), py::arg("pos"), py::arg("aim_quat"),
           py::arg("cur_pose"));
+    // what SimManager(scene_path=maps) would make of the list (mpenv_maps_plan): no GPU, no manager.  A
+    // list the engine refuses raises with its message.
+    m.def("maps_plan", [](py::object maps, uint32_t team_size, uint32_t sim_flags, Task task_type) {
+        std::vector<std::string> paths;
+        const std::vector<mpenv_map_range> ranges = mapRanges(maps, paths);
+        mpenv_config cfg = {};
+        cfg.exec_mode = MPENV_EXEC_CUDA;
+        cfg.team_size = team_size;
+        cfg.sim_flags = sim_flags;
+        cfg.task_type = (int32_t)task_type;
+        for (const mpenv_map_range &r : ranges) cfg.num_worlds += r.num_worlds;
+        std::vector<mpenv_map_desc> desc(std::max<size_t>(ranges.size(), 1));
+        int32_t track = 0;
+        check(mpenv_maps_plan(&cfg, ranges.data(), (int32_t)ranges.size(), desc.data(), &track));
+        py::list out;
+        for (size_t r = 0; r < ranges.size(); r++)
+            out.append(py::dict(py::arg("path") = paths[r], py::arg("first_world") = desc[r].first_world,
+                                py::arg("num_worlds") = desc[r].num_worlds, py::arg("scene") = desc[r].scene,
+                                py::arg("residency") = residencyName(desc[r].residency)));
+        return py::dict(py::arg("maps") = out, py::arg("spawn_track_len") = track);
+    }, py::arg("maps"), py::arg("team_size"), py::arg("sim_flags") = 0, py::arg("task_type") = Task::Zone);
     m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;

@@ -571,7 +571,7 @@ QuirkGrid quirkGrid(const std::vector<Vec3> &verts, float r, float margin, float
 // (only the traversal cost changes), but they were tuned for one triangle
 // set: the file names the FNV-1a 64 of its collisions.bin and is ignored
 // for any other.
-static uint64_t fnv1a64File(const std::string &path)
+uint64_t fnv1a64File(const std::string &path)
 {
     std::ifstream f(path, std::ios::binary);
     uint64_t h = 1469598103934665603ull;

@@ -117,6 +117,10 @@ struct IoError : std::runtime_error {
 // map_importer.cpp:229-231).
 Scene loadScene(const std::string &scene_dir, bool spawn_in_middle = false);
 
+// FNV-1a 64 of a file's bytes: how lidar_tree.txt names its collisions.bin,
+// and how a map set's checkpoint header names each scene (manager.cpp).
+uint64_t fnv1a64File(const std::string &path);
+
 // Dedups, triangulates and links the navmesh and builds/reads its A* table.
 void buildNavMesh(Scene &s, const std::string &navmesh_path);
 

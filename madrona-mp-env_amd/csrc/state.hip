@@ -315,9 +315,11 @@ __global__ void __launch_bounds__(256) k_state_copy(StateTab *tab, char *blob, i
 
 // One block.  The blob's header must equal this manager's byte for byte
 // (magic, version, W, N, T, track length, flags, task, bytes, sections and
-// the reserved zeros); every map entry must be -1 or a world.  go = 1 only
-// when both hold; otherwise the error bits are raised and the load that
-// follows on the stream returns at once.
+// the reserved words: zeros, or a map set's layout hash); every map entry
+// must be -1 or a world, and on a map-set manager a world of the same scene
+// as its destination (MPENV_STATE_ERR_CROSS_MAP).  go = 1 only when all
+// hold; otherwise the error bits are raised and the load that follows on the
+// stream returns at once.
 __global__ void __launch_bounds__(256) k_state_check(StateTab *tab, const char *src, const int32_t *map)
 {
     __shared__ uint32_t bad;
@@ -334,6 +336,18 @@ __global__ void __launch_bounds__(256) k_state_check(StateTab *tab, const char *
         const int32_t n4 = W / 4;
         const int4 *m4 = reinterpret_cast<const int4 *>(map);
         auto outside = [W](int32_t s) { return s < -1 || s >= W; };
+        // map sets: world d may take snapshot world s only when both play the
+        // same scene (the blob's range layout is this manager's: the header
+        // check); the table reads follow the range check of s
+        const int32_t *mow = tab->mapOfWorld;
+        // the table is handed out (mpenv_map_of_world): an entry a caller
+        // overwrote still indexes inside rangeScene
+        auto sceneOf = [mow, tab](int32_t w) { return tab->rangeScene[(uint32_t)mow[w] % MPENV_MAX_MAP_RANGES]; };
+        auto crossMap = [sceneOf](int32_t d, int32_t s) { return sceneOf(d) != sceneOf(s); };
+        auto entry = [&](int32_t d, int32_t s) -> uint32_t {
+            if (outside(s)) return MPENV_STATE_ERR_MAP;
+            return mow && s >= 0 && crossMap(d, s) ? MPENV_STATE_ERR_CROSS_MAP : 0u;
+        };
         for (int32_t base = 0; base < n4; base += 4 * 256) {
             int4 v[4];
 #pragma unroll
@@ -342,11 +356,14 @@ __global__ void __launch_bounds__(256) k_state_check(StateTab *tab, const char *
                 v[j] = i < n4 ? m4[i] : make_int4(-1, -1, -1, -1);
             }
 #pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (outside(v[j].x) || outside(v[j].y) || outside(v[j].z) || outside(v[j].w)) mine |= MPENV_STATE_ERR_MAP;
+            for (int j = 0; j < 4; j++) {
+                // -1 for the lanes past n4: never a table read
+                const int32_t d0 = 4 * (base + j * 256 + (int32_t)threadIdx.x);
+                mine |= entry(d0, v[j].x) | entry(d0 + 1, v[j].y) | entry(d0 + 2, v[j].z) | entry(d0 + 3, v[j].w);
+            }
         }
         const int32_t d = n4 * 4 + (int32_t)threadIdx.x; // W % 4 entries left
-        if (d < W && outside(map[d])) mine |= MPENV_STATE_ERR_MAP;
+        if (d < W) mine |= entry(d, map[d]);
     }
     if (mine) atomicOr(&bad, mine);
     __syncthreads();
