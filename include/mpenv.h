@@ -310,6 +310,8 @@ static_assert(sizeof(mpenv_packed_step_snapshot) == 192, "PackedStepSnapshot lay
 #define MPENV_DTYPE_UINT8 3
 #define MPENV_DTYPE_UINT16 4
 #define MPENV_DTYPE_UINT64 5
+/* the league's standings table (mpenv_league_tensor) only */
+#define MPENV_DTYPE_INT64 6
 
 typedef struct mpenv_config {
     int32_t exec_mode;          /* MPENV_EXEC_* */
@@ -700,6 +702,10 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
 /* map sets, one batch over several maps: mpenv_map_range, mpenv_map_desc, mpenv_create_maps,
  * mpenv_num_maps, mpenv_map_info, mpenv_map_of_world, mpenv_maps_plan and MPENV_STATE_ERR_CROSS_MAP */
 #include "mpenv_maps.h"
+/* the league scheduler, standings and matchmaking on the device: mpenv_league_config,
+ * mpenv_league_enable / _disable / _enabled / _tensor / _clear / _set_weights, and mpenv_league_layout,
+ * mpenv_league_draw and mpenv_league_record without a manager */
+#include "mpenv_league.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

@@ -290,6 +290,37 @@ public:
     {
         return static_cast<uint8_t *>(cameraImage(MPENV_CAMERA_LABEL, dims));
     }
+    // extension: the league scheduler (mpenv_league.h): standings int64 [P+1][P+1][8] and, by draw mode,
+    // a weighted redraw of the policy ids of every world that ends an episode, behind every step and init.
+    // Needs auto_reset; enableLeague again replaces the league.
+    void enableLeague(int numPolicies, int32_t draw = MPENV_LEAGUE_DRAW_TEAM1, uint32_t seed = 0)
+    {
+        const mpenv_league_config c { numPolicies, draw, seed, 0 };
+        check(mpenv_league_enable(mgr_, &c));
+    }
+    void disableLeague() { check(mpenv_league_disable(mgr_)); }
+    // whether a league is enabled, and (cfg non-null) its configuration
+    bool leagueConfig(mpenv_league_config *cfg = nullptr) const
+    {
+        int32_t on = 0;
+        check(mpenv_league_enabled(mgr_, cfg, &on));
+        return on != 0;
+    }
+    // device pointers and dims (may be null); they hold until the next enableLeague or disableLeague
+    int64_t *leagueTable(int64_t *dims = nullptr) const
+    {
+        return static_cast<int64_t *>(leagueTensor(MPENV_LEAGUE_TABLE, dims));
+    }
+    int32_t *leagueWeights(int64_t *dims = nullptr) const
+    {
+        return static_cast<int32_t *>(leagueTensor(MPENV_LEAGUE_WEIGHTS, dims));
+    }
+    uint32_t *leagueDraws(int64_t *dims = nullptr) const
+    {
+        return static_cast<uint32_t *>(leagueTensor(MPENV_LEAGUE_DRAWS, dims));
+    }
+    // zeroes the table; asynchronous on strm (null: the manager's own stream)
+    void clearLeague(void *strm = nullptr) { check(mpenv_league_clear(mgr_, strm)); }
     // every agent through policyId's checkpoint
     void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
     {
@@ -428,6 +459,16 @@ private:
         int32_t dtype = 0, ndim = 0;
         int64_t d[8] = {};
         check(mpenv_camera_tensor(mgr_, which, &p, &dtype, &ndim, d, nullptr));
+        for (int k = 0; dims && k < ndim; k++) dims[k] = d[k];
+        return p;
+    }
+
+    void *leagueTensor(int32_t which, int64_t *dims) const
+    {
+        void *p = nullptr;
+        int32_t dtype = 0, ndim = 0;
+        int64_t d[8] = {};
+        check(mpenv_league_tensor(mgr_, which, &p, &dtype, &ndim, d, nullptr));
         for (int k = 0; dims && k < ndim; k++) dims[k] = d[k];
         return p;
     }

@@ -224,6 +224,9 @@ void mpenv_manager::runStep(hipStream_t st)
     // groups' join, over the whole batch); behind the captured graph, which
     // enabling or disabling a camera leaves alone
     if (camOn) renderCamera(st);
+    // the league's standings and redraws for the worlds the step ended: one
+    // launch over the whole batch, behind the graph as the camera is
+    if (leagueOn) runLeague(st, false);
     postStep(st);
 }
 
@@ -359,6 +362,7 @@ void mpenv_manager::runInitGraph(hipStream_t st)
         for (const MapRange &r : ranges) initRange(r.S, r.sc, scenes[r.scene].img);
     else initRange(S, sc, img);
     if (camOn) renderCamera(st);
+    if (leagueOn) runLeague(st, true); // every world draws, none is recorded
 }
 
 template <typename T>

@@ -1,4 +1,4 @@
-// manager.h — what manager.cpp, manager_scene.cpp and camera.cpp share, and
+// manager.h — what manager.cpp, manager_scene.cpp, camera.cpp and league.cpp share, and
 // nothing else includes: the error channel of the C ABI, the owning HIP handle types and
 // struct mpenv_manager.
 #pragma once
@@ -15,6 +15,7 @@
 
 #include "camera.h"
 #include "engine.h"
+#include "league.h"
 #include "mpenv.h"
 #include "policy.h"
 #include "scene.h"
@@ -321,6 +322,15 @@ struct mpenv_manager {
     mpenv_camera_config camCfg {};
     CameraDev cam {};
     DevPtr camBuf;
+    // The league scheduler (league.cpp, mpenv_league.h; DESIGN.md §2
+    // definition 20): one allocation for the standings table, the weights
+    // and the draw counters.  While on, every step and init is followed by
+    // k_league on its stream, outside the captured graph; no part of the
+    // state, the snapshots, the wire format or the graph's key.
+    bool leagueOn = false;
+    mpenv_league_config leagueCfg {};
+    LeagueDev league {};
+    DevPtr leagueBuf;
 
     ~mpenv_manager();
 
@@ -358,6 +368,7 @@ struct mpenv_manager {
     void setupGroups(int want);
     void runInitGraph(hipStream_t st);
     void renderCamera(hipStream_t st); // camera.cpp
+    void runLeague(hipStream_t st, bool initOnly); // league.cpp
     bool exportDesc(int32_t id, TensorDesc &d);
     void *exportPtr(int32_t id);
     void gatherDebug(bool explore = false);

@@ -73,9 +73,10 @@ struct PyTensor {
         mt->dl_tensor.data = ptr;
         mt->dl_tensor.device = { gpu >= 0 ? kDLROCM : kDLCPU, gpu >= 0 ? gpu : 0 };
         mt->dl_tensor.ndim = (int32_t)dims.size();
-        // kDLInt 0, kDLUInt 1, kDLFloat 2; the camera's label image is the one 8-bit tensor
+        // kDLInt 0, kDLUInt 1, kDLFloat 2; the camera's label image is the one 8-bit tensor, the
+        // league's standings table the one 64-bit (signed) one
         uint8_t code = dtype == MPENV_DTYPE_FLOAT32 ? 2 : (dtype == MPENV_DTYPE_UINT32 || dtype == MPENV_DTYPE_UINT8 ? 1 : 0);
-        mt->dl_tensor.dtype = { code, (uint8_t)(dtype == MPENV_DTYPE_UINT8 ? 8 : 32), 1 };
+        mt->dl_tensor.dtype = { code, (uint8_t)(dtype == MPENV_DTYPE_UINT8 ? 8 : dtype == MPENV_DTYPE_INT64 ? 64 : 32), 1 };
         mt->dl_tensor.shape = ctx->shape.data();
         mt->dl_tensor.strides = nullptr;
         mt->dl_tensor.byte_offset = 0;
@@ -118,7 +119,28 @@ struct PySimManager {
         t.dims.assign(dims, dims + ndim);
         return t;
     }
+
+    // the league's table, weights or draws (mpenv_league.h)
+    PyTensor leagueTensor(int32_t which) const
+    {
+        PyTensor t;
+        t.owner = h;
+        int32_t ndim = 0;
+        int64_t dims[8];
+        check(mpenv_league_tensor(h->mgr, which, &t.ptr, &t.dtype, &ndim, dims, &t.gpu));
+        t.dims.assign(dims, dims + ndim);
+        return t;
+    }
 };
+
+// "none" / "team1" / "both" <-> MPENV_LEAGUE_DRAW_*
+const char *const kLeagueDrawNames[] = { "none", "team1", "both" };
+int32_t leagueDrawOf(const std::string &name)
+{
+    for (int32_t k = 0; k < 3; k++)
+        if (name == kLeagueDrawNames[k]) return k;
+    throw py::value_error("draw must be \"none\", \"team1\" or \"both\"");
+}
 
 // Unscoped so that pybind11 generates |, &, ^ (sim_flags |= SimFlags.X,
 // scripts/jax_train.py:80-100).
@@ -212,6 +234,7 @@ PYBIND11_MODULE(madrona_mp_env, m)
             return t.dtype == MPENV_DTYPE_FLOAT32  ? "float32"
                    : t.dtype == MPENV_DTYPE_UINT32 ? "uint32"
                    : t.dtype == MPENV_DTYPE_UINT8  ? "uint8"
+                   : t.dtype == MPENV_DTYPE_INT64  ? "int64"
                                                    : "int32";
         })
         .def_property_readonly("gpu_id", [](const PyTensor &t) { return t.gpu; })
@@ -468,6 +491,35 @@ PYBIND11_MODULE(madrona_mp_env, m)
         }, py::arg("stream") = 0)
         .def("camera_depth", [](PySimManager &s) { return s.cameraTensor(MPENV_CAMERA_DEPTH); })
         .def("camera_label", [](PySimManager &s) { return s.cameraTensor(MPENV_CAMERA_LABEL); })
+        // the league scheduler (mpenv_league.h): standings int64 [P+1, P+1, 8] and, by draw mode, a
+        // weighted redraw of the policy ids of every world that ends an episode, behind every step and init
+        .def("enable_league", [](PySimManager &s, int32_t num_policies, const std::string &draw, uint32_t seed) {
+            const mpenv_league_config c { num_policies, leagueDrawOf(draw), seed, 0 };
+            check(mpenv_league_enable(s.h->mgr, &c));
+        }, py::arg("num_policies"), py::arg("draw") = "team1", py::arg("seed") = 0)
+        .def("disable_league", [](PySimManager &s) { check(mpenv_league_disable(s.h->mgr)); })
+        // (num_policies, draw, seed), or None while disabled
+        .def("league_config", [](PySimManager &s) -> py::object {
+            mpenv_league_config c {};
+            int32_t on = 0;
+            check(mpenv_league_enabled(s.h->mgr, &c, &on));
+            if (!on) return py::none();
+            return py::make_tuple(c.num_policies, std::string(kLeagueDrawNames[c.draw]), c.seed);
+        })
+        .def("league_table", [](PySimManager &s) { return s.leagueTensor(MPENV_LEAGUE_TABLE); })
+        .def("league_weights", [](PySimManager &s) { return s.leagueTensor(MPENV_LEAGUE_WEIGHTS); })
+        .def("league_draws", [](PySimManager &s) { return s.leagueTensor(MPENV_LEAGUE_DRAWS); })
+        .def("clear_league", [](PySimManager &s, uintptr_t stream) {
+            check(mpenv_league_clear(s.h->mgr, reinterpret_cast<void *>(stream)));
+        }, py::arg("stream") = 0)
+        .def("set_league_weights", [](PySimManager &s, py::array_t<int32_t, py::array::c_style | py::array::forcecast> w) {
+            mpenv_league_config c {};
+            int32_t on = 0;
+            check(mpenv_league_enabled(s.h->mgr, &c, &on));
+            if (on && w.size() != (py::ssize_t)(c.num_policies + 1) * c.num_policies)
+                throw py::value_error("set_league_weights: weights must be [num_policies + 1, num_policies]");
+            check(mpenv_league_set_weights(s.h->mgr, w.data()));
+        }, py::arg("weights"))
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
         .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
         .def("graph_status", [](PySimManager &s) {
@@ -682,6 +734,41 @@ PYBIND11_MODULE(madrona_mp_env, m)
                                 py::arg("residency") = residencyName(desc[r].residency)));
         return py::dict(py::arg("maps") = out, py::arg("spawn_track_len") = track);
     }, py::arg("maps"), py::arg("team_size"), py::arg("sim_flags") = 0, py::arg("task_type") = Task::Zone);
+    // the league's arithmetic without a GPU (mpenv_league.h): league_draw performs visit n of global
+    // world `world` on ids [2, team_size] (weights [P+1, P], None: all 1) and returns the new ids;
+    // league_record adds one ended episode (match_result: its first five values) to table
+    // [P+1, P+1, 8] int64 in place and returns it
+    m.def("league_draw", [](int32_t num_policies, const std::string &draw, uint32_t seed, uint32_t world, uint32_t n,
+                            py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, py::object weights) {
+        const mpenv_league_config c { num_policies, leagueDrawOf(draw), seed, 0 };
+        int64_t unused = 0;
+        check(mpenv_league_layout(&c, 1, &unused, nullptr, nullptr)); // the configuration, before sizes are checked by it
+        if (ids.ndim() != 2 || ids.shape(0) != 2) throw py::value_error("league_draw: ids must be [2, team_size]");
+        py::array_t<int32_t> out({ ids.shape(0), ids.shape(1) });
+        std::copy(ids.data(), ids.data() + ids.size(), out.mutable_data());
+        py::array_t<int32_t, py::array::c_style | py::array::forcecast> w;
+        if (!weights.is_none()) {
+            w = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(weights);
+            if (!w || w.size() != (py::ssize_t)(num_policies + 1) * num_policies)
+                throw py::value_error("league_draw: weights must be [num_policies + 1, num_policies]");
+        }
+        check(mpenv_league_draw(&c, world, n, weights.is_none() ? nullptr : w.data(), (int32_t)ids.shape(1),
+                                out.mutable_data()));
+        return out;
+    }, py::arg("num_policies"), py::arg("draw"), py::arg("seed"), py::arg("world"), py::arg("n"), py::arg("ids"),
+          py::arg("weights") = py::none());
+    m.def("league_record", [](int32_t num_policies, py::array_t<int32_t, py::array::c_style | py::array::forcecast> match_result,
+                              py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids,
+                              py::array_t<int64_t, py::array::c_style> table) {
+        const mpenv_league_config c { num_policies, MPENV_LEAGUE_DRAW_NONE, 0, 0 };
+        int64_t bytes = 0;
+        check(mpenv_league_layout(&c, 1, &bytes, nullptr, nullptr));
+        if (match_result.size() < 5) throw py::value_error("league_record: match_result needs five values");
+        if (ids.ndim() != 2 || ids.shape(0) != 2) throw py::value_error("league_record: ids must be [2, team_size]");
+        if (table.nbytes() != bytes) throw py::value_error("league_record: table must be int64 [P + 1, P + 1, 8]");
+        check(mpenv_league_record(&c, match_result.data(), ids.data(), (int32_t)ids.shape(1), table.mutable_data()));
+        return table;
+    }, py::arg("num_policies"), py::arg("match_result"), py::arg("ids"), py::arg("table"));
     m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;
