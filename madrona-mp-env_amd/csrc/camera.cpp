@@ -27,11 +27,7 @@ constexpr size_t kTabBytes = 2 * mp::kCameraMaxDim * sizeof(float);
 
 void mpenv_manager::renderCamera(hipStream_t st)
 {
-    if (!mapSet()) {
-        launched(launchCamera(S, sc, img, cam, st), "k_camera launch failed");
-        return;
-    }
-    // a map set: each range against its own scene, into its agents' images
+    // each range against its own scene, into its agents' images
     for (const MapRange &r : ranges) {
         CameraDev rc = cam;
         const int64_t px = (int64_t)r.w0 * S.N * cam.height * cam.width;

@@ -151,8 +151,11 @@ void mpenv_manager::record(hipStream_t st)
 // The Step graph over one world range on one stream.  With timing on,
 // kNumTimedKernels + 1 events bracket the kernels (one segment per
 // range per step, contiguous in the pool).
-void mpenv_manager::stepRange(const DevState &R, const SceneDev &rsc, const SceneImages &img, hipStream_t st)
+void mpenv_manager::stepRange(const MapRange &r, hipStream_t st)
 {
+    const DevState &R = r.S;
+    const SceneDev &rsc = r.sc;
+    const SceneImages &img = scenes[r.scene].img;
     record(st);
     launched(launchMove(R, rsc, img, st), "k_move launch failed");
     record(st);
@@ -240,20 +243,13 @@ std::vector<char> mpenv_manager::argKey() const
     put(&groups, sizeof(groups));
     put(&lidarBranch, sizeof(lidarBranch));
     put(&lidarIters, sizeof(lidarIters));
-    // on a map-set manager nothing launches with these three (S is the
-    // whole batch, sc and img range 0's scene): a dead part of its key
-    put(&S, sizeof(S));
-    put(&sc, sizeof(sc));
-    put(&img, sizeof(img));
-    for (const DevState &G : gS) put(&G, sizeof(G));
-    for (const SceneDev &g : gsc) put(&g, sizeof(g));
-    // a map set: every range's three structs (none for a single-map manager,
-    // whose key is the bytes above)
-    for (const MapRange &r : ranges) {
-        put(&r.S, sizeof(r.S));
-        put(&r.sc, sizeof(r.sc));
-        put(&scenes[r.scene].img, sizeof(SceneImages));
-    }
+    // the three structs every stepRange launches with
+    for (const std::vector<MapRange> *v : { &ranges, &groupRanges })
+        for (const MapRange &r : *v) {
+            put(&r.S, sizeof(r.S));
+            put(&r.sc, sizeof(r.sc));
+            put(&scenes[r.scene].img, sizeof(SceneImages));
+        }
     return k;
 }
 
@@ -326,25 +322,21 @@ bool mpenv_manager::captureStep()
 
 void mpenv_manager::launchStepDirect(hipStream_t st)
 {
-    if (mapSet()) {
-        // the ranges are the groups: in range order on the one stream
-        for (const MapRange &r : ranges) stepRange(r.S, r.sc, scenes[r.scene].img, st);
-        return;
-    }
     if (groups <= 1) {
-        stepRange(S, sc, img, st);
+        // in range order on the one stream
+        for (const MapRange &r : ranges) stepRange(r, st);
         return;
     }
     // group 0 runs on the caller's stream itself, so G groups occupy G
     // hardware queues (GPU_MAX_HW_QUEUES is 4 per process by default)
     HIP_CHECK(hipEventRecord(forkEv, st));
-    for (int i = 1; i < groups; i++) gside[i].startAfter(forkEv);
+    for (const SideStream &g : gside) g.startAfter(forkEv);
     for (int i = 1; i < groups; i++) {
-        stepRange(gS[i], gsc[i], img, gside[i].stream);
-        gside[i].markDone();
+        stepRange(groupRanges[i], gside[i - 1].stream);
+        gside[i - 1].markDone();
     }
-    stepRange(gS[0], gsc[0], img, st);
-    for (int i = 1; i < groups; i++) gside[i].joinInto(st);
+    stepRange(groupRanges[0], st);
+    for (const SideStream &g : gside) g.joinInto(st);
 }
 
 void mpenv_manager::runInitGraph(hipStream_t st)
@@ -352,15 +344,13 @@ void mpenv_manager::runInitGraph(hipStream_t st)
     // triggerReset on every world (mgr.cpp:1936-1938) then the Init graph
     // (sim.cpp:5322-5340): resetSystem + observations + lidar.
     HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)S.reset, 1, (size_t)S.W, st));
-    auto initRange = [&](const DevState &R, const SceneDev &rsc, const SceneImages &rimg) {
-        launched(launchResetOnly(R, rsc, st), "k_reset launch failed");
-        launched(launchVisibility(R, rsc, rimg, st), "k_vis launch failed");
-        launched(launchObservations(R, rsc, st), "k_obs launch failed");
-        launched(launchLidar(R, rsc, rimg, lidarItersOf(R), st), "k_lidar launch failed");
-    };
-    if (mapSet())
-        for (const MapRange &r : ranges) initRange(r.S, r.sc, scenes[r.scene].img);
-    else initRange(S, sc, img);
+    for (const MapRange &r : ranges) {
+        const SceneImages &rimg = scenes[r.scene].img;
+        launched(launchResetOnly(r.S, r.sc, st), "k_reset launch failed");
+        launched(launchVisibility(r.S, r.sc, rimg, st), "k_vis launch failed");
+        launched(launchObservations(r.S, r.sc, st), "k_obs launch failed");
+        launched(launchLidar(r.S, r.sc, rimg, lidarItersOf(r.S), st), "k_lidar launch failed");
+    }
     if (camOn) renderCamera(st);
     if (leagueOn) runLeague(st, true); // every world draws, none is recorded
 }
@@ -473,7 +463,7 @@ static void allocState(mpenv_manager &m)
 #undef MP_ALLOC_WI
 #undef MP_ALLOC_WF
     // T and trackLen: the run-time row shapes of the buffer table (engine.h)
-    const int64_t T = S.T, trackLen = m.sc.spawnTrackLen;
+    const int64_t T = S.T, trackLen = m.firstScene().sc.spawnTrackLen;
 #define MP_ALLOC(n, type, kind, ...) S.n = m.alloc<type>((size_t)(bufRows(kind, S.W, S.N) * rowElems(__VA_ARGS__)));
 #define MP_ALLOC_E(n, type, kind, id, ...) MP_ALLOC(n, type, kind, __VA_ARGS__)
     S.dmg = m.alloc<float>(A * kMaxTeamSize);
@@ -502,22 +492,25 @@ static void allocState(mpenv_manager &m)
         if (!b.ptr) throw std::runtime_error(std::string("device buffer ") + b.name + " was not allocated");
 }
 
+// The log flags go into the scene's SceneDev: before any range or group is
+// cut from it.
 static void openLogs(mpenv_manager &m, const mpenv_config *cfg)
 {
     DevState &S = m.S;
+    SceneDev &sc = m.firstScene().sc;
     const size_t W = (size_t)S.W;
     S.evStride = 2 * S.N + 1;
     if (cfg->replay_log_path) {
         m.replayFile = std::fopen(cfg->replay_log_path, "rb");
         if (!m.replayFile) throw IoError(std::string("cannot open replay log ") + cfg->replay_log_path);
         S.replayLog = m.alloc<mpenv_step_log>(W);
-        m.sc.replayOn = 1;
+        sc.replayOn = 1;
     }
     if (cfg->record_log_path) {
         m.recordFile = std::fopen(cfg->record_log_path, "wb");
         if (!m.recordFile) throw IoError(std::string("cannot open record log ") + cfg->record_log_path);
         S.recordLog = m.alloc<mpenv_step_log>(W);
-        m.sc.recordOn = 1;
+        sc.recordOn = 1;
     }
     if (m.replayFile || m.recordFile) m.hostLog.assign(W, mpenv_step_log {});
     if (cfg->event_log_path) {
@@ -530,7 +523,7 @@ static void openLogs(mpenv_manager &m, const mpenv_config *cfg)
         m.hostEvents.assign(W * S.evStride, mpenv_game_event {});
         m.hostSnaps.assign(W, mpenv_packed_step_snapshot {});
         m.hostSnapWritten.assign(W, 0);
-        m.sc.eventsOn = 1;
+        sc.eventsOn = 1;
     }
 }
 
@@ -575,26 +568,35 @@ void mpenv_manager::setupGroups(int want)
     // the new split is built aside and swapped in whole: a throw leaves the
     // previous one in place; the previous one goes with the locals
     // at most 3 (4 measured slower: 66 vs 86 M agent-steps/s at C3)
-    const int n = std::max(1, std::min(std::min(want, 3), S.W));
+    const MapRange &all = ranges[0];
+    const int n = std::max(1, std::min(std::min(want, 3), all.n));
     Event fork;
     std::vector<SideStream> side;
-    std::vector<DevState> rS;
-    std::vector<SceneDev> rsc;
+    std::vector<MapRange> cut;
     if (n > 1) fork = Event::create(hipEventDisableTiming);
     for (int i = 0; i < n && n > 1; i++) {
-        const int64_t w0 = (int64_t)S.W * i / n, w1 = (int64_t)S.W * (i + 1) / n;
-        DevState G;
-        SceneDev gs;
-        sliceState(S, sc, w0, w1 - w0, G, gs);
-        rS.push_back(G);
-        rsc.push_back(gs);
-        side.push_back(SideStream::create());
+        const int64_t w0 = (int64_t)all.n * i / n, w1 = (int64_t)all.n * (i + 1) / n;
+        MapRange g;
+        g.scene = all.scene;
+        g.w0 = all.w0 + (int32_t)w0;
+        g.n = (int32_t)(w1 - w0);
+        sliceState(all.S, all.sc, w0, w1 - w0, g.S, g.sc);
+        cut.push_back(g);
+        if (i > 0) side.push_back(SideStream::create());
     }
     groups = n;
     std::swap(forkEv, fork);
     gside.swap(side);
-    gS.swap(rS);
-    gsc.swap(rsc);
+    groupRanges.swap(cut);
+}
+
+// Workload counters on (the buffer) or off (null): in the batch and in every
+// slice a kernel launches with.
+void mpenv_manager::setStats(unsigned long long *p)
+{
+    S.stats = p;
+    for (MapRange &r : ranges) r.S.stats = p;
+    for (MapRange &g : groupRanges) g.S.stats = p;
 }
 
 // Live managers: the XLA targets receive a manager pointer inside opaque
@@ -628,8 +630,8 @@ int32_t mpenv_abi_version(void) { return MPENV_ABI_VERSION; }
 
 const char *mpenv_last_error(void) { return g_last_error.c_str(); }
 
-// mpenv_create (plan null: cfg->scene_path) and mpenv_create_maps (the
-// planned list, cfg->scene_path null).
+// mpenv_create (plan null: cfg->scene_path as one scene and one range over
+// the batch) and mpenv_create_maps (the planned list, cfg->scene_path null).
 static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager **out)
 {
     if (cfg->exec_mode != MPENV_EXEC_CUDA)
@@ -656,33 +658,38 @@ static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager *
         m->S.outTab = nullptr;
         m->S.outBase = 0;
         m->cfg = *cfg;
-        m->scenePath = plan ? plan->scenes[plan->ranges[0].scene].path : std::string(cfg->scene_path);
-        m->cfg.scene_path = m->scenePath.c_str();
         m->gpu = cfg->gpu_id;
+        m->fromList = plan != nullptr;
         // A blocking stream: ordered after work the caller queued on the
         // legacy default stream (e.g. torch writes into the action tensors),
         // matching the synchronous Manager::step contract (mgr.cpp:1949-1960).
         m->stream = Stream::create(hipStreamDefault);
-        if (plan) {
-            // the per-scene device work once per loaded scene; spawnTrackLen,
-            // a row shape of the buffer table, is the set's largest in every
-            // SceneDev (a range whose own value is smaller leaves the rows'
-            // tails at their reset fill)
-            m->scenes = std::move(plan->scenes);
-            for (MapScene &ms : m->scenes) {
-                buildSceneDev(*m, ms.scene, ms.limits, ms.sc, ms.img);
-                ms.sc.spawnTrackLen = plan->spawnTrackLen;
-            }
-            const MapScene &first = m->scenes[plan->ranges[0].scene];
-            m->sc = first.sc;
-            m->img = first.img;
-            m->limits = first.limits;
-        } else {
-            m->scene = loadScene(m->scenePath, (cfg->sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
-            m->limits = sceneLimits(m->scene);
-            if (!m->limits.supported) return fail(MPENV_ERR_UNSUPPORTED, "scene not supported: " + m->limits.reason);
-            buildSceneDev(*m, m->scene, m->limits, m->sc, m->img);
+        MapPlan one; // mpenv_create: the one scene, the one range over the batch
+        if (!plan) {
+            MapScene ms;
+            ms.path = cfg->scene_path;
+            ms.scene = loadScene(ms.path, (cfg->sim_flags & MPENV_SIMFLAG_SPAWN_IN_MIDDLE) != 0);
+            ms.limits = sceneLimits(ms.scene);
+            if (!ms.limits.supported) return fail(MPENV_ERR_UNSUPPORTED, "scene not supported: " + ms.limits.reason);
+            one.scenes.push_back(std::move(ms));
+            MapRange all;
+            all.n = (int32_t)cfg->num_worlds;
+            one.ranges.push_back(all);
+            plan = &one;
         }
+        m->scenes = std::move(plan->scenes);
+        m->ranges = std::move(plan->ranges); // scene, w0, n; cut below
+        m->cfg.scene_path = m->firstScene().path.c_str(); // the string at its final address
+        // the per-scene device work once per loaded scene; spawnTrackLen, a
+        // row shape of the buffer table, is the plan's largest in every
+        // SceneDev (a range whose own value is smaller leaves the rows'
+        // tails at their reset fill)
+        int32_t trackLen = 0;
+        for (MapScene &ms : m->scenes) {
+            buildSceneDev(*m, ms.scene, ms.limits, ms.sc, ms.img);
+            trackLen = std::max(trackLen, ms.sc.spawnTrackLen);
+        }
+        for (MapScene &ms : m->scenes) ms.sc.spawnTrackLen = trackLen;
         m->S.W = (int32_t)cfg->num_worlds;
         m->S.T = (int32_t)cfg->team_size;
         m->S.N = 2 * m->S.T;
@@ -697,12 +704,14 @@ static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager *
                           : cfg->event_log_path  ? "a manager opened with event_log_path"
                                                  : nullptr;
         m->stateTabDev = m->alloc<StateTab>(1);
-        buildStateTab(m->S, m->sc, m->stateTabDev, m->stateTab);
-        if (plan) {
-            // the ranges as complete engines, the world -> range table, and
-            // the checkpoint header's hash of the layout (reserved[0..1];
-            // zeros for a single-map manager): FNV-1a 64 over each range's
-            // world count and its scene's collisions.bin hash
+        buildStateTab(m->S, m->firstScene().sc, m->stateTabDev, m->stateTab);
+        // the ranges as complete engines
+        for (MapRange &r : m->ranges) sliceState(m->S, m->scenes[r.scene].sc, r.w0, r.n, r.S, r.sc);
+        if (m->mapSet()) {
+            // from a list: the world -> range table, and the checkpoint
+            // header's hash of the layout (reserved[0..1]; zeros for a manager
+            // from mpenv_create, whose table mpenv_map_of_world makes): FNV-1a
+            // 64 over each range's world count and its scene's collisions.bin hash
             std::vector<int32_t> mow((size_t)m->S.W);
             uint64_t h = 1469598103934665603ull;
             auto mix = [&h](uint64_t v) {
@@ -711,10 +720,8 @@ static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager *
                     h *= 1099511628211ull;
                 }
             };
-            for (size_t k = 0; k < plan->ranges.size(); k++) {
-                MapRange r = plan->ranges[k];
-                sliceState(m->S, m->scenes[r.scene].sc, r.w0, r.n, r.S, r.sc);
-                m->ranges.push_back(r);
+            for (size_t k = 0; k < m->ranges.size(); k++) {
+                const MapRange &r = m->ranges[k];
                 std::fill(mow.begin() + r.w0, mow.begin() + r.w0 + r.n, (int32_t)k);
                 m->stateTab.rangeScene[k] = r.scene;
                 mix((uint64_t)r.n);
@@ -738,7 +745,7 @@ static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager *
             // 1.215; profiles/r05e_ab_world_groups.jsonl).
             int want = 1;
             if (const char *e = std::getenv("MPENV_WORLD_GROUPS")) want = std::atoi(e);
-            m->setupGroups(plan ? 1 : want); // a map set's ranges are its groups
+            m->setupGroups(m->mapSet() ? 1 : want); // a map set's ranges are its groups
         }
         if (const char *e = std::getenv("MPENV_SCENE_RESIDENCY")) {
             const std::string v = e;
@@ -749,16 +756,14 @@ static int createManager(const mpenv_config *cfg, MapPlan *plan, mpenv_manager *
                 throw std::runtime_error("MPENV_SCENE_RESIDENCY=" + v + ": " + g_last_error);
         }
         if (const char *e = std::getenv("MPENV_STEP_GRAPH")) m->useGraph = std::atoi(e) != 0;
-        if (const char *e = plan ? nullptr : std::getenv("MPENV_LIDAR_BRANCH"))
+        if (const char *e = m->mapSet() ? nullptr : std::getenv("MPENV_LIDAR_BRANCH"))
             if (std::atoi(e) != 0 && mpenv_set_lidar_branch(m.get(), 1) != MPENV_OK) throw std::runtime_error(g_last_error);
         // TrainControl from sim flags (mgr.cpp:1397-1413)
         int32_t tc[3] = { (cfg->sim_flags & MPENV_SIMFLAG_SIM_EVAL_MODE) ? 1 : 0,
                           (cfg->sim_flags & MPENV_SIMFLAG_STAGGER_STARTS) ? 1 : 0,
                           (cfg->sim_flags & MPENV_SIMFLAG_RANDOM_FLIP_TEAMS) ? 1 : 0 };
         HIP_CHECK(hipMemcpyAsync(m->S.trainCtrl, tc, sizeof(tc), hipMemcpyHostToDevice, m->stream));
-        if (m->mapSet())
-            for (const MapRange &r : m->ranges) launched(launchConstruct(r.S, r.sc, tc, m->stream), "construct launch failed");
-        else launched(launchConstruct(m->S, m->sc, tc, m->stream), "construct launch failed");
+        for (const MapRange &r : m->ranges) launched(launchConstruct(r.S, r.sc, tc, m->stream), "construct launch failed");
         HIP_CHECK(hipStreamSynchronize(m->stream));
         liveAdd(m.get());
         *out = m.release();
@@ -798,31 +803,25 @@ static int mapSetRefused(const mpenv_manager *m, const char *what, const char *w
 int mpenv_num_maps(mpenv_manager *m, int32_t *n)
 {
     if (!m || !n) return fail(MPENV_ERR_INVALID, "null argument");
-    *n = m->mapSet() ? (int32_t)m->ranges.size() : 1;
+    *n = (int32_t)m->ranges.size();
     return MPENV_OK;
 }
 
 int mpenv_map_info(mpenv_manager *m, int32_t range, mpenv_map_desc *out, const char **scene_path)
 {
     if (!m || !out) return fail(MPENV_ERR_INVALID, "null argument");
-    const int32_t n = m->mapSet() ? (int32_t)m->ranges.size() : 1;
+    const int32_t n = (int32_t)m->ranges.size();
     if (range < 0 || range >= n)
         return fail(MPENV_ERR_INVALID, "map range " + std::to_string(range) + " is outside [0, " + std::to_string(n) + ")");
     std::memset(out, 0, sizeof(*out));
     out->supported = 1;
-    const SceneImages *img = &m->img;
-    if (m->mapSet()) {
-        const MapRange &r = m->ranges[(size_t)range];
-        out->first_world = r.w0;
-        out->num_worlds = r.n;
-        out->scene = r.scene;
-        img = &m->scenes[r.scene].img;
-        if (scene_path) *scene_path = m->scenes[r.scene].path.c_str();
-    } else {
-        out->num_worlds = m->S.W;
-        if (scene_path) *scene_path = m->scenePath.c_str();
-    }
-    out->residency = img->residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+    const MapRange &r = m->ranges[(size_t)range];
+    const MapScene &ms = m->scenes[r.scene];
+    out->first_world = r.w0;
+    out->num_worlds = r.n;
+    out->scene = r.scene;
+    if (scene_path) *scene_path = ms.path.c_str();
+    out->residency = ms.img.residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
     return MPENV_OK;
 }
 
@@ -830,7 +829,7 @@ int mpenv_map_of_world(mpenv_manager *m, void **dev_ptr)
 {
     if (!m || !dev_ptr) return fail(MPENV_ERR_INVALID, "null argument");
     return guarded([&] {
-        // a single-map manager: all zeros, made on first use
+        // a manager from mpenv_create: all zeros, made on first use
         if (!m->mapOfWorld) {
             m->mapOfWorld = m->alloc<int32_t>((size_t)m->S.W);
             HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -1064,7 +1063,8 @@ int mpenv_debug_trace_rays(mpenv_manager *m, const float *o, const float *d, int
 {
     if (!m || !o || !d || !t_out || !hit_out || n < 0) return fail(MPENV_ERR_INVALID, "bad argument");
     hipStream_t st = streamOf(m, stream);
-    if (launchTraceRays(m->sc, m->img, o, d, n, mode, t_out, hit_out, st) || hipStreamSynchronize(st) != hipSuccess)
+    const MapScene &ms = m->firstScene();
+    if (launchTraceRays(ms.sc, ms.img, o, d, n, mode, t_out, hit_out, st) || hipStreamSynchronize(st) != hipSuccess)
         return fail(MPENV_ERR_HIP, "trace-ray launch failed");
     return MPENV_OK;
 }
@@ -1084,7 +1084,8 @@ int mpenv_debug_geom_queries(mpenv_manager *m, int32_t mode, int32_t n, const mp
     if (mode == MPENV_GEOM_STUCK) ok = ok && q->sel && q->bound && n % 64 == 0;
     if (!ok) return fail(MPENV_ERR_INVALID, "bad geometry query");
     hipStream_t st = streamOf(m, stream);
-    if (launchGeomQueries(m->sc, m->img, mode, n, *q, st) || hipStreamSynchronize(st) != hipSuccess)
+    const MapScene &ms = m->firstScene();
+    if (launchGeomQueries(ms.sc, ms.img, mode, n, *q, st) || hipStreamSynchronize(st) != hipSuccess)
         return fail(MPENV_ERR_HIP, "geometry-query launch failed");
     return MPENV_OK;
 }
@@ -1200,7 +1201,7 @@ int mpenv_wire_pack(mpenv_manager *m, void *dst, int32_t keyframe, void *stream)
     if (!m || !dst) return fail(MPENV_ERR_INVALID, "null argument");
     if (int rc = mapSetRefused(m, "mpenv_wire_pack", kWireWhy)) return rc;
     if ((uintptr_t)dst & 15u) return fail(MPENV_ERR_INVALID, "wire message buffer must be 16-B aligned");
-    if (launchWirePack(m->S, static_cast<char *>(dst), keyframe != 0, m->sc.worldOffset, streamOf(m, stream)))
+    if (launchWirePack(m->S, static_cast<char *>(dst), keyframe != 0, m->firstScene().sc.worldOffset, streamOf(m, stream)))
         return fail(MPENV_ERR_HIP, "wire pack launch failed");
     return MPENV_OK;
 }
@@ -1213,8 +1214,8 @@ int mpenv_wire_unpack(mpenv_manager *m, const void *src, int32_t keyframe, void 
     void *st = streamOf(m, stream);
     const int W = m->S.W;
     int32_t *prev = m->wireEp + (size_t)m->wireParity * W, *next = m->wireEp + (size_t)(m->wireParity ^ 1) * W;
-    if (launchWireUnpack(m->S, m->sc, static_cast<const char *>(src), keyframe != 0, m->wireErr, m->sc.worldOffset,
-                         prev, next, st))
+    const SceneDev &sc = m->firstScene().sc;
+    if (launchWireUnpack(m->S, sc, static_cast<const char *>(src), keyframe != 0, m->wireErr, sc.worldOffset, prev, next, st))
         return fail(MPENV_ERR_HIP, "wire unpack launch failed");
     m->wireParity ^= 1;
     return MPENV_OK;
@@ -1285,7 +1286,7 @@ int mpenv_state_dims(mpenv_manager *m, uint32_t *num_worlds, uint32_t *team_size
     if (!m) return fail(MPENV_ERR_INVALID, "null argument");
     if (num_worlds) *num_worlds = (uint32_t)m->S.W;
     if (team_size) *team_size = (uint32_t)m->S.T;
-    if (spawn_track_len) *spawn_track_len = (uint32_t)m->sc.spawnTrackLen;
+    if (spawn_track_len) *spawn_track_len = (uint32_t)m->firstScene().sc.spawnTrackLen;
     return MPENV_OK;
 }
 
@@ -1597,26 +1598,22 @@ int mpenv_set_scene_residency(mpenv_manager *m, int32_t mode)
     if (mode != MPENV_SCENE_AUTO && mode != MPENV_SCENE_LDS && mode != MPENV_SCENE_GLOBAL)
         return fail(MPENV_ERR_INVALID, "scene residency must be MPENV_SCENE_AUTO, MPENV_SCENE_LDS or MPENV_SCENE_GLOBAL "
                                        "(MPENV_SCENE_RESIDENCY=auto|lds|global)");
-    if (mode == MPENV_SCENE_LDS && !m->limits.ldsOk && !m->mapSet())
-        return fail(MPENV_ERR_INVALID, "scene does not fit the LDS-resident path: " + m->limits.ldsWhyNot);
-    // a map set: every scene, or (one that does not fit, named) none
+    // every scene, or (one that does not fit; a list names it) none
     for (size_t r = 0; mode == MPENV_SCENE_LDS && r < m->ranges.size(); r++) {
         const MapScene &ms = m->scenes[m->ranges[r].scene];
-        if (!ms.limits.ldsOk)
-            return fail(MPENV_ERR_INVALID, "map range " + std::to_string(r) + " (" + ms.path +
-                                               ") does not fit the LDS-resident path: " + ms.limits.ldsWhyNot);
+        if (ms.limits.ldsOk) continue;
+        const std::string which = m->mapSet() ? "map range " + std::to_string(r) + " (" + ms.path + ")" : "scene";
+        return fail(MPENV_ERR_INVALID, which + " does not fit the LDS-resident path: " + ms.limits.ldsWhyNot);
     }
     return guarded([&] {
         // the kernels of a step in flight keep the path they were launched
         // on; the step graph is keyed on every img (argKey) and re-captured
         HIP_CHECK(hipStreamSynchronize(m->stream));
         m->residencyMode = mode;
-        auto pick = [mode](const SceneLimits &l) {
-            const bool lds = mode == MPENV_SCENE_LDS || (mode == MPENV_SCENE_AUTO && l.ldsOk);
-            return lds ? kResidencyLds : kResidencyGlobal;
-        };
-        m->img.residency = pick(m->limits); // a map set: range 0's scene, as the test hooks read it
-        for (MapScene &ms : m->scenes) ms.img.residency = pick(ms.limits);
+        for (MapScene &ms : m->scenes) {
+            const bool lds = mode == MPENV_SCENE_LDS || (mode == MPENV_SCENE_AUTO && ms.limits.ldsOk);
+            ms.img.residency = lds ? kResidencyLds : kResidencyGlobal;
+        }
     });
 }
 
@@ -1625,7 +1622,7 @@ int mpenv_scene_residency(mpenv_manager *m, int32_t *mode_in_use)
     if (!m || !mode_in_use) return fail(MPENV_ERR_INVALID, "null argument");
     if (m->mapSet())
         return fail(MPENV_ERR_INVALID, "mpenv_scene_residency: a map set has a residency per map (mpenv_map_info)");
-    *mode_in_use = m->img.residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
+    *mode_in_use = m->firstScene().img.residency == kResidencyLds ? MPENV_SCENE_LDS : MPENV_SCENE_GLOBAL;
     return MPENV_OK;
 }
 
@@ -1756,10 +1753,7 @@ int mpenv_enable_stats(mpenv_manager *m, int32_t enable)
         if (enable && !m->statsBuf) m->statsBuf = m->alloc<unsigned long long>(kNumStats);
         if (enable) HIP_CHECK(hipMemsetAsync(m->statsBuf, 0, sizeof(unsigned long long) * kNumStats, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
-        unsigned long long *p = enable ? m->statsBuf : nullptr;
-        m->S.stats = p;
-        for (DevState &G : m->gS) G.stats = p;
-        for (MapRange &r : m->ranges) r.S.stats = p;
+        m->setStats(enable ? m->statsBuf : nullptr);
     });
 }
 
@@ -1795,9 +1789,9 @@ int mpenv_kernel_timings(mpenv_manager *m, int32_t max_n, const char **names, fl
             }
             steps++;
         }
-        // a map set records one segment per range and step: each kernel's
-        // time is summed over the ranges
-        if (m->mapSet()) steps /= (int)m->ranges.size();
+        // one segment per range and step: each kernel's time is summed over
+        // the ranges (world groups, each a segment too, are not divided out)
+        steps /= (int)m->ranges.size();
         m->eventsUsed = 0;
         for (int k = 0; k < nk && k < max_n; k++) {
             if (names) names[k] = kernelName(k);

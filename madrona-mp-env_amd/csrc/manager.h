@@ -43,9 +43,9 @@ void buildSceneDev(mpenv_manager &m, const Scene &s, const SceneLimits &limits, 
 // manager_scene.cpp: why cfg's task or flags rule the scene out ("": they do not)
 std::string sceneTaskProblem(const Scene &s, const mpenv_config &cfg);
 
-// Map sets (mpenv_maps.h; DESIGN.md §2 definition 19).  One loaded scene: what
-// a single-map manager keeps in scenePath / scene / sc / img / limits.  sc
-// holds the manager's world_id_offset and the set's common spawnTrackLen.
+// Scenes and world ranges (mpenv_maps.h; DESIGN.md §2 definition 19).  One
+// loaded scene; sc holds the manager's world_id_offset and the largest
+// spawnTrackLen of the manager's scenes.
 struct MapScene {
     std::string path;
     Scene scene;
@@ -54,7 +54,9 @@ struct MapScene {
     SceneLimits limits;
     uint64_t collisionsHash = 0; // FNV-1a 64 of collisions.bin (scene.h)
 };
-// One range: worlds [w0, w0 + n) as a complete engine (sliceState) on scenes[scene]
+// One range: worlds [w0, w0 + n) as a complete engine (sliceState) on
+// scenes[scene].  A manager's `ranges` tile its batch; a world group is a
+// sub-range of ranges[0].
 struct MapRange {
     int32_t scene = 0, w0 = 0, n = 0;
     DevState S {};
@@ -202,41 +204,40 @@ struct TensorDesc {
 // graph's executable before every stream, the main stream last.
 struct mpenv_manager {
     mpenv_config cfg;
-    std::string scenePath;
     int gpu = 0;
-    Scene scene;
-    SceneDev sc;
-    // the global-resident images and the path in use (manager_scene.cpp);
-    // part of the step graph's key
-    SceneImages img {};
     int32_t residencyMode = MPENV_SCENE_AUTO; // as asked for
-    SceneLimits limits;
-    DevState S;
+    DevState S; // the whole batch: exports, checkpoints, wire, policy, league
     Stream stream;
     std::vector<void *> allocations;
-    // Map sets: empty for a manager from mpenv_create, which runs on the
-    // members above alone.  For one from mpenv_create_maps the step, the
-    // init, the construct and the camera loop over `ranges` in order on the
-    // call's stream, and sc / img / limits / scenePath above are range 0's
-    // scene (the ray and geometry test hooks answer for it).
+    // The loaded scenes and the world ranges that tile the batch: one of
+    // each, {scene 0, world 0, W}, from mpenv_create; the planned list from
+    // mpenv_create_maps.  The step, the init, the construct and the camera
+    // loop over `ranges` in order on the call's stream.  A scene's img (the
+    // residency in use) is part of the step graph's key.
     std::vector<MapScene> scenes;
     std::vector<MapRange> ranges;
+    // range 0's scene: what the ray and geometry test hooks, the wire calls,
+    // the log flags and the buffer table's trackLen read
+    MapScene &firstScene() { return scenes[ranges[0].scene]; }
     int32_t *mapOfWorld = nullptr; // device [W]: range index per world (mpenv_map_of_world)
-    bool mapSet() const { return !ranges.empty(); }
+    // created from a list (of one range or more): what the refusals, the
+    // checkpoint header's layout hash and the env overrides at create go by
+    bool fromList = false;
+    bool mapSet() const { return fromList; }
 
     // Debug gather buffers (allocated lazily)
     float *dbgAF = nullptr, *dbgWF = nullptr, *dbgCrumbs = nullptr;
     int32_t *dbgAI = nullptr, *dbgWI = nullptr;
     uint32_t *dbgExplore = nullptr;
 
-    // World groups: contiguous world ranges stepped on their own streams
-    // (fork/join with events) so independent kernels overlap on the GPU.
-    // One fork event starts every group; group 0 runs on the caller's
-    // stream, so gside[0] is made (as it always was) and never used.
+    // World groups: ranges[0] cut into contiguous sub-ranges (groupRanges;
+    // none for one group) stepped on their own streams (fork/join with
+    // events) so independent kernels overlap on the GPU.  One fork event
+    // starts every group; group 0 runs on the caller's stream, group i > 0
+    // on gside[i - 1].
     int groups = 1;
     std::vector<SideStream> gside;
-    std::vector<DevState> gS;
-    std::vector<SceneDev> gsc;
+    std::vector<MapRange> groupRanges;
     Event forkEv;
     // One group only: k_lidar on a branch stream beside k_vis -> k_obs (no
     // data dependence between them after k_sim).  MPENV_LIDAR_BRANCH=1.
@@ -357,7 +358,7 @@ struct mpenv_manager {
     void allocPolicyWork();
     void setPolicySlot(int slot, const float *blob);
     void record(hipStream_t st);
-    void stepRange(const DevState &R, const SceneDev &rsc, const SceneImages &rimg, hipStream_t st);
+    void stepRange(const MapRange &r, hipStream_t st);
     void preStep(hipStream_t st);
     void postStep(hipStream_t st);
     void runStep(hipStream_t st);
@@ -366,6 +367,7 @@ struct mpenv_manager {
     bool captureStep();
     void launchStepDirect(hipStream_t st);
     void setupGroups(int want);
+    void setStats(unsigned long long *p);
     void runInitGraph(hipStream_t st);
     void renderCamera(hipStream_t st); // camera.cpp
     void runLeague(hipStream_t st, bool initOnly); // league.cpp
