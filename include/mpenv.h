@@ -706,6 +706,10 @@ int mpenv_debug_policy_dense(mpenv_manager *mgr, const float *x_device, int32_t 
  * mpenv_league_enable / _disable / _enabled / _tensor / _clear / _set_weights, and mpenv_league_layout,
  * mpenv_league_draw and mpenv_league_record without a manager */
 #include "mpenv_league.h"
+/* the live curriculum pool, episode starts harvested on the device: mpenv_curriculum_pool_config,
+ * mpenv_curriculum_pool_enable / _disable / _enabled / _tensor / _tick / _set / _configure, and
+ * mpenv_curriculum_pool_layout, _select and _pack without a manager */
+#include "mpenv_curriculum.h"
 
 /* Measurement hook: how many times the Step graph has been captured (the
  * graph is re-captured whenever a kernel argument struct changes: world

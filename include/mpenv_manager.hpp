@@ -321,6 +321,47 @@ public:
     }
     // zeroes the table; asynchronous on strm (null: the manager's own stream)
     void clearLeague(void *strm = nullptr) { check(mpenv_league_clear(mgr_, strm)); }
+    // extension: the live curriculum pool (mpenv_curriculum.h): [ranges][capacity] snapshots in device
+    // memory that episode starts read in place, refreshed behind every step from the running batch.
+    // After init(); enableCurriculumPool again replaces the pool.
+    void enableCurriculumPool(int capacity, int period = 64, int stepLo = 0, int stepHi = 2999 /* episodeLen - 1 */,
+                              uint32_t need = 0, uint32_t seed = 0)
+    {
+        const mpenv_curriculum_pool_config c { capacity, period, stepLo, stepHi, need, seed };
+        check(mpenv_curriculum_pool_enable(mgr_, &c));
+    }
+    void disableCurriculumPool() { check(mpenv_curriculum_pool_disable(mgr_)); }
+    // period, window, need and seed; cfg.capacity must be the enabled one
+    void configureCurriculumPool(const mpenv_curriculum_pool_config &cfg)
+    {
+        check(mpenv_curriculum_pool_configure(mgr_, &cfg));
+    }
+    // whether a pool is enabled, and (cfg non-null) its configuration
+    bool curriculumPoolConfig(mpenv_curriculum_pool_config *cfg = nullptr) const
+    {
+        int32_t on = 0;
+        check(mpenv_curriculum_pool_enabled(mgr_, cfg, &on));
+        return on != 0;
+    }
+    // device pointers and dims (may be null); they hold until the next enable or disable
+    mpenv_curriculum_snapshot *curriculumPool(int64_t *dims = nullptr) const
+    {
+        return static_cast<mpenv_curriculum_snapshot *>(curriculumPoolTensor(MPENV_CURRICULUM_POOL, dims));
+    }
+    uint32_t *curriculumPoolTicks(int64_t *dims = nullptr) const
+    {
+        return static_cast<uint32_t *>(curriculumPoolTensor(MPENV_CURRICULUM_TICKS, dims));
+    }
+    uint32_t curriculumPoolTick() const
+    {
+        uint32_t t = 0;
+        check(mpenv_curriculum_pool_tick(mgr_, &t));
+        return t;
+    }
+    void setCurriculumPool(const mpenv_curriculum_snapshot *host, int n, int mapRange = 0, int firstSlot = 0)
+    {
+        check(mpenv_curriculum_pool_set(mgr_, mapRange, firstSlot, n, host));
+    }
     // every agent through policyId's checkpoint
     void policyForward(float *logits, int32_t *actions = nullptr, void *strm = nullptr, int policyId = 0)
     {
@@ -469,6 +510,16 @@ private:
         int32_t dtype = 0, ndim = 0;
         int64_t d[8] = {};
         check(mpenv_league_tensor(mgr_, which, &p, &dtype, &ndim, d, nullptr));
+        for (int k = 0; dims && k < ndim; k++) dims[k] = d[k];
+        return p;
+    }
+
+    void *curriculumPoolTensor(int32_t which, int64_t *dims) const
+    {
+        void *p = nullptr;
+        int32_t dtype = 0, ndim = 0;
+        int64_t d[8] = {};
+        check(mpenv_curriculum_pool_tensor(mgr_, which, &p, &dtype, &ndim, d, nullptr));
         for (int k = 0; dims && k < ndim; k++) dims[k] = d[k];
         return p;
     }

@@ -28,11 +28,11 @@ EXT = os.path.join(PKG, "madrona_mp_env" + sysconfig.get_config_var("EXT_SUFFIX"
 ORACLE_LIB = os.path.join(ORACLE, "_build", "liboracle.so")
 
 LIB_SOURCES = ["kernels.hip", "move.hip", "vis.hip", "obs.hip", "lidar.hip", "hooks.hip", "wire.hip", "state.hip",
-               "policy.hip", "camera.hip", "league.hip", "manager.cpp", "manager_scene.cpp", "camera.cpp", "league.cpp",
-               "policy.cpp", "scene.cpp", "navmesh.cpp"]
+               "policy.hip", "camera.hip", "league.hip", "curriculum.hip", "manager.cpp", "manager_scene.cpp",
+               "camera.cpp", "league.cpp", "curriculum.cpp", "policy.cpp", "scene.cpp", "navmesh.cpp"]
 API_HEADERS = [os.path.join(INCLUDE, h) for h in ("mpenv.h", "mpenv_policy_slots.h", "mpenv_policy_precision.h",
                                                      "mpenv_scene_residency.h", "mpenv_camera.h", "mpenv_maps.h",
-                                                     "mpenv_league.h")]
+                                                     "mpenv_league.h", "mpenv_curriculum.h")]
 MAX_PARALLEL = 16  # what one command may use on the GPU machines, whatever the machine's CPU count
 
 

@@ -21,6 +21,7 @@
 // All traversals read an LDS-resident copy of the BVH (geom_dev.h).  Every
 // arithmetic expression follows the reference (and the CPU oracle) term by
 // term with -ffp-contract=off so that results are bit-identical.
+#include "curriculum_core.h"
 #include "nav_dev.h"
 #include "sight_dev.h"
 
@@ -29,6 +30,8 @@
 namespace mpenv {
 
 using namespace mp;
+
+static_assert(kCrouch == mp::kPoseCrouch && kProne == mp::kPoseProne, "curriculum_core.h restates the pose ids");
 
 // Zone and goal-region frames, once at scene upload (see FrameDev).
 __global__ void k_scene_frames(SceneTables *tab)
@@ -1527,32 +1530,19 @@ __device__ void writeSnapshotD(const DevState &S, const SceneDev &sc, int w, boo
     sn.num_events = (uint32_t)logged;
     sn.event_mask = (uint32_t)emask;
     sn.match_id = matchIdD(S, sc, w);
-    sn.step = (uint16_t)S.curStep[w];
-    sn.cur_zone = (uint8_t)S.curZone[w];
-    sn.cur_zone_controller = (int8_t)(S.captured[w] ? S.controlling[w] : -1);
-    sn.zone_steps_remaining = (uint16_t)S.zoneSteps[w];
-    sn.steps_until_point = (uint16_t)S.stepsUntilPoint[w];
+    // the match state and the players as curriculum_core.h packs them (the
+    // curriculum pool's k_harvest runs the same lines); curStep is still the
+    // value the step began with
+    mp::curriculumPackMatch(sn, S.curStep[w], S.curZone[w], S.captured[w], S.controlling[w], S.zoneSteps[w],
+                            S.stepsUntilPoint[w]);
     for (int i = 0; i < kMaxAgents; i++) {
-        mpenv_packed_player &pl = sn.players[i];
         if (i >= N) {
-            pl = mpenv_packed_player {};
+            sn.players[i] = mpenv_packed_player {};
             continue;
         }
         const int64_t g = g0 + i;
-        // float -> i16 through i32 (in range except yaw == +pi, which wraps)
-        pl.pos[0] = (int16_t)(int32_t)S.px[g];
-        pl.pos[1] = (int16_t)(int32_t)S.py[g];
-        pl.pos[2] = (int16_t)(int32_t)S.pz[g];
-        pl.yaw = (int16_t)(int32_t)(S.ayaw[g] * 32768 / kPi);
-        pl.pitch = (int16_t)(int32_t)(S.apitch[g] * 32768 / kPi);
-        pl.mag_num_bullets = (uint8_t)(uint16_t)S.magazine[2 * g];
-        pl.is_reloading = (uint8_t)S.magazine[2 * g + 1];
-        pl.hp = (uint8_t)S.hp[g];
-        uint8_t fl = 0;
-        if (S.landedOn[g] != -1) fl |= 2;
-        if (S.curPose[g] == kCrouch) fl |= 4;
-        else if (S.curPose[g] == kProne) fl |= 8;
-        pl.flags = fl;
+        sn.players[i] = mp::curriculumPackPlayer(S.px[g], S.py[g], S.pz[g], S.ayaw[g], S.apitch[g], S.hp[g],
+                                                 S.magazine[2 * g], S.magazine[2 * g + 1], S.curPose[g], S.landedOn[g]);
     }
     S.snapshots[w] = sn;
     S.evLogged[w] = 0;

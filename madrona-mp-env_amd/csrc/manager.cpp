@@ -230,6 +230,9 @@ void mpenv_manager::runStep(hipStream_t st)
     // the league's standings and redraws for the worlds the step ended: one
     // launch over the whole batch, behind the graph as the camera is
     if (leagueOn) runLeague(st, false);
+    // the curriculum pool's refresh from the state the step left: one launch
+    // over the pool's slots, behind the graph as well
+    if (poolOn) runHarvest(st);
     postStep(st);
 }
 
@@ -353,6 +356,7 @@ void mpenv_manager::runInitGraph(hipStream_t st)
     }
     if (camOn) renderCamera(st);
     if (leagueOn) runLeague(st, true); // every world draws, none is recorded
+    inited = true;
 }
 
 template <typename T>

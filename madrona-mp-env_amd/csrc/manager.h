@@ -1,4 +1,4 @@
-// manager.h — what manager.cpp, manager_scene.cpp, camera.cpp and league.cpp share, and
+// manager.h — what manager.cpp, manager_scene.cpp, camera.cpp, league.cpp and curriculum.cpp share, and
 // nothing else includes: the error channel of the C ABI, the owning HIP handle types and
 // struct mpenv_manager.
 #pragma once
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "camera.h"
+#include "curriculum.h"
 #include "engine.h"
 #include "league.h"
 #include "mpenv.h"
@@ -332,6 +333,19 @@ struct mpenv_manager {
     mpenv_league_config leagueCfg {};
     LeagueDev league {};
     DevPtr leagueBuf;
+    // The live curriculum pool (curriculum.cpp, mpenv_curriculum.h; DESIGN.md
+    // §2 definition 21): one allocation for the snapshots, their ticks and
+    // the range table.  While on, every range's (and group's) sc.curriculum
+    // points into it -- scenes[].sc keeps what creation set, which disable
+    // restores -- and every step is followed by k_harvest on its stream,
+    // outside the captured graph.  No part of the state, the snapshots or the
+    // wire format.  `inited`: an init has run (the pool is filled from the batch).
+    bool inited = false;
+    bool poolOn = false;
+    mpenv_curriculum_pool_config poolCfg {};
+    PoolDev pool {};
+    DevPtr poolBuf;
+    uint32_t poolTick = 0; // harvests since enable
 
     ~mpenv_manager();
 
@@ -371,6 +385,7 @@ struct mpenv_manager {
     void runInitGraph(hipStream_t st);
     void renderCamera(hipStream_t st); // camera.cpp
     void runLeague(hipStream_t st, bool initOnly); // league.cpp
+    void runHarvest(hipStream_t st); // curriculum.cpp
     bool exportDesc(int32_t id, TensorDesc &d);
     void *exportPtr(int32_t id);
     void gatherDebug(bool explore = false);

@@ -131,7 +131,33 @@ struct PySimManager {
         t.dims.assign(dims, dims + ndim);
         return t;
     }
+
+    // the curriculum pool or its ticks (mpenv_curriculum.h)
+    PyTensor poolTensor(int32_t which) const
+    {
+        PyTensor t;
+        t.owner = h;
+        int32_t ndim = 0;
+        int64_t dims[8];
+        check(mpenv_curriculum_pool_tensor(h->mgr, which, &t.ptr, &t.dtype, &ndim, dims, &t.gpu));
+        t.dims.assign(dims, dims + ndim);
+        return t;
+    }
 };
+
+// step_range None: the whole episode, (0, episode_len - 1)
+constexpr int32_t kPyEpisodeLen = 3000; // consts.hpp episodeLen
+mpenv_curriculum_pool_config poolConfigOf(int32_t capacity, int32_t period, const py::object &step_range, uint32_t need,
+                                          uint32_t seed)
+{
+    int32_t lo = 0, hi = kPyEpisodeLen - 1;
+    if (!step_range.is_none()) {
+        const auto r = step_range.cast<std::pair<int32_t, int32_t>>();
+        lo = r.first;
+        hi = r.second;
+    }
+    return { capacity, period, lo, hi, need, seed };
+}
 
 // "none" / "team1" / "both" <-> MPENV_LEAGUE_DRAW_*
 const char *const kLeagueDrawNames[] = { "none", "team1", "both" };
@@ -520,6 +546,60 @@ PYBIND11_MODULE(madrona_mp_env, m)
                 throw py::value_error("set_league_weights: weights must be [num_policies + 1, num_policies]");
             check(mpenv_league_set_weights(s.h->mgr, w.data()));
         }, py::arg("weights"))
+        // the live curriculum pool (mpenv_curriculum.h): [R, capacity] snapshots in device memory that
+        // episode starts read in place, refreshed behind every step from the running batch
+        .def("enable_curriculum_pool", [](PySimManager &s, int32_t capacity, int32_t period, py::object step_range,
+                                          uint32_t need, uint32_t seed) {
+            const mpenv_curriculum_pool_config c = poolConfigOf(capacity, period, step_range, need, seed);
+            check(mpenv_curriculum_pool_enable(s.h->mgr, &c));
+        }, py::arg("capacity"), py::arg("period") = 64, py::arg("step_range") = py::none(), py::arg("need") = 0,
+             py::arg("seed") = 0)
+        .def("disable_curriculum_pool", [](PySimManager &s) { check(mpenv_curriculum_pool_disable(s.h->mgr)); })
+        // capacity stays; an argument left None keeps its value
+        .def("configure_curriculum_pool", [](PySimManager &s, py::object period, py::object step_range, py::object need,
+                                             py::object seed) {
+            mpenv_curriculum_pool_config c {};
+            int32_t on = 0;
+            check(mpenv_curriculum_pool_enabled(s.h->mgr, &c, &on));
+            if (!period.is_none()) c.period = period.cast<int32_t>();
+            if (!step_range.is_none()) {
+                const auto r = step_range.cast<std::pair<int32_t, int32_t>>();
+                c.step_lo = r.first;
+                c.step_hi = r.second;
+            }
+            if (!need.is_none()) c.need = need.cast<uint32_t>();
+            if (!seed.is_none()) c.seed = seed.cast<uint32_t>();
+            if (!on) c.capacity = 1; // a valid configuration, so that the refusal names the disabled pool
+            check(mpenv_curriculum_pool_configure(s.h->mgr, &c));
+        }, py::arg("period") = py::none(), py::arg("step_range") = py::none(), py::arg("need") = py::none(),
+             py::arg("seed") = py::none())
+        // dict(capacity, period, step_range, need, seed), or None while disabled
+        .def("curriculum_pool_config", [](PySimManager &s) -> py::object {
+            mpenv_curriculum_pool_config c {};
+            int32_t on = 0;
+            check(mpenv_curriculum_pool_enabled(s.h->mgr, &c, &on));
+            if (!on) return py::none();
+            return py::dict(py::arg("capacity") = c.capacity, py::arg("period") = c.period,
+                            py::arg("step_range") = py::make_tuple(c.step_lo, c.step_hi), py::arg("need") = c.need,
+                            py::arg("seed") = c.seed);
+        })
+        // zero-copy: uint8 [R, capacity, 176] and uint32 [R, capacity]
+        .def("curriculum_pool", [](PySimManager &s) { return s.poolTensor(MPENV_CURRICULUM_POOL); })
+        .def("curriculum_pool_ticks", [](PySimManager &s) { return s.poolTensor(MPENV_CURRICULUM_TICKS); })
+        .def("curriculum_pool_tick", [](PySimManager &s) {
+            uint32_t t = 0;
+            check(mpenv_curriculum_pool_tick(s.h->mgr, &t));
+            return t;
+        })
+        // array: snapshots as mpenv_curriculum.SNAPSHOT records or uint8 [n, 176]
+        .def("curriculum_pool_set", [](PySimManager &s, py::array array, int32_t map_range, int32_t first_slot) {
+            py::array a = py::array::ensure(array, py::array::c_style);
+            if (!a || a.nbytes() == 0 || a.nbytes() % (py::ssize_t)sizeof(mpenv_curriculum_snapshot) != 0)
+                throw py::value_error("curriculum_pool_set: array must hold whole 176-byte snapshots, C-contiguous");
+            check(mpenv_curriculum_pool_set(s.h->mgr, map_range, first_slot,
+                                            (int32_t)(a.nbytes() / (py::ssize_t)sizeof(mpenv_curriculum_snapshot)),
+                                            static_cast<const mpenv_curriculum_snapshot *>(a.data())));
+        }, py::arg("array"), py::arg("map_range") = 0, py::arg("first_slot") = 0)
         .def("set_lidar_branch", [](PySimManager &s, bool on) { check(mpenv_set_lidar_branch(s.h->mgr, on ? 1 : 0)); })
         .def("set_lidar_iters", [](PySimManager &s, int32_t n) { check(mpenv_set_lidar_iters(s.h->mgr, n)); })
         .def("graph_status", [](PySimManager &s) {
@@ -769,6 +849,43 @@ PYBIND11_MODULE(madrona_mp_env, m)
         check(mpenv_league_record(&c, match_result.data(), ids.data(), (int32_t)ids.shape(1), table.mutable_data()));
         return table;
     }, py::arg("num_policies"), py::arg("match_result"), py::arg("ids"), py::arg("table"));
+    // the curriculum pool's arithmetic without a GPU (mpenv_curriculum.h): curriculum_pool_select says
+    // whether slot `slot` of range `range` refreshes at `tick` and names its candidate world;
+    // curriculum_pool_pack packs one world (n = 2 * team_size agents) into its 176 bytes
+    m.def("curriculum_pool_select", [](uint32_t seed, uint32_t world_id_offset, uint32_t range, uint32_t slot,
+                                       uint32_t tick, int32_t period, int32_t first_world, int32_t num_worlds) {
+        int32_t refresh = 0, world = -1;
+        check(mpenv_curriculum_pool_select(seed, world_id_offset, range, slot, tick, period, first_world, num_worlds,
+                                           &refresh, &world));
+        return py::make_tuple(refresh != 0, world);
+    }, py::arg("seed"), py::arg("world_id_offset"), py::arg("range"), py::arg("slot"), py::arg("tick"), py::arg("period"),
+          py::arg("first_world"), py::arg("num_worlds"));
+    m.def("curriculum_pool_pack", [](int32_t cur_step, int32_t cur_zone, int32_t captured, int32_t controlling,
+                                     int32_t zone_steps, int32_t steps_until_point,
+                                     py::array_t<float, py::array::c_style | py::array::forcecast> pos,
+                                     py::array_t<float, py::array::c_style | py::array::forcecast> yaw,
+                                     py::array_t<float, py::array::c_style | py::array::forcecast> pitch,
+                                     py::array_t<float, py::array::c_style | py::array::forcecast> hp,
+                                     py::array_t<int32_t, py::array::c_style | py::array::forcecast> magazine,
+                                     py::array_t<int32_t, py::array::c_style | py::array::forcecast> cur_pose,
+                                     py::array_t<int32_t, py::array::c_style | py::array::forcecast> landed_on) {
+        const py::ssize_t n = yaw.size();
+        if (n < 2 || n > 12 || n % 2 != 0) throw py::value_error("curriculum_pool_pack: 2 * team_size agents, team_size in [1, 6]");
+        if (pos.size() != 3 * n || pitch.size() != n || hp.size() != n || magazine.size() != 2 * n || cur_pose.size() != n ||
+            landed_on.size() != n)
+            throw py::value_error("curriculum_pool_pack: pos [n, 3], magazine [n, 2], the rest [n]");
+        const mpenv_curriculum_world w { cur_step, cur_zone, captured, controlling, zone_steps, steps_until_point,
+                                         pos.data(), yaw.data(), pitch.data(), hp.data(), magazine.data(), cur_pose.data(),
+                                         landed_on.data() };
+        py::array_t<uint8_t> out((py::ssize_t)sizeof(mpenv_curriculum_snapshot));
+        check(mpenv_curriculum_pool_pack(&w, (int32_t)(n / 2), reinterpret_cast<mpenv_curriculum_snapshot *>(out.mutable_data())));
+        return out;
+    }, py::arg("cur_step"), py::arg("cur_zone"), py::arg("captured"), py::arg("controlling"), py::arg("zone_steps"),
+          py::arg("steps_until_point"), py::arg("pos"), py::arg("yaw"), py::arg("pitch"), py::arg("hp"), py::arg("magazine"),
+          py::arg("cur_pose"), py::arg("landed_on"));
+    m.attr("CURRICULUM_NEED_CAPTURED") = MPENV_CURRICULUM_NEED_CAPTURED;
+    m.attr("CURRICULUM_NEED_CONTESTED") = MPENV_CURRICULUM_NEED_CONTESTED;
+    m.attr("CURRICULUM_NEED_BOTH_ALIVE") = MPENV_CURRICULUM_NEED_BOTH_ALIVE;
     m.def("policy_check", [](const std::string &dir) { check(mpenv_policy_check(dir.c_str())); }, py::arg("dir"));
     m.def("state_section", [](int32_t idx, uint32_t num_worlds, uint32_t team_size, uint32_t spawn_track_len) {
         const char *name = nullptr;
